@@ -7,8 +7,13 @@ expected_pii_type context.  A "step" = one pii_scan_redact_device call over the 
 HBM before timing; outputs are written to HBM.  Multi-GPU: conversations are sharded by
 conversation id (each rank owns its own 100k conversations, weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline figure needs: set up, W warmup steps, K timed steps, the result
+line.  --full adds what takes runs of its own: the CPU baseline (unless --no-cpu-baseline), the
+per-stage probe steps after the timed region (stages_ms) and config 5's one-stream k_scan pass.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -253,6 +258,56 @@ class DeviceBatch:
                                   self.ctx.data_ptr())
 
 
+DUMP_SEED = 20240607       # the samples of dump_outputs are the same in every run
+DUMP_ROWS = 1 << 20        # rows sampled for out_offs / ctx       (8 + 4 MB)
+DUMP_BYTES = 1 << 22       # output byte positions sampled         (16 MB)
+DUMP_SPANS = 400_000       # spans sampled, 6 fields each          (19 MB)
+
+
+def _dump_sample(n: int, k: int, rng) -> np.ndarray:
+    """all of 0..n-1 when n <= k, else k of them, ascending"""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(rng.choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path: str, B, out_bytes: int, n_spans: int, hist: np.ndarray):
+    """What a caller of the timed path receives from its last step, as <path>/<name>.npy: the redacted
+    bytes (out_bytes.npy, f32), the per-row output offsets (out_offs.npy, f64; row i's text is
+    out[offs[i]:offs[i+1]]) and context types (ctx.npy, f32), the spans (spans.npy, f64 [k, 6]: utt,
+    start, end, info_type, likelihood, flags), the per-infoType histogram with the span total last
+    (histogram.npy, f64) and [output bytes, spans] (totals.npy, f64).  Arrays larger than their DUMP_*
+    size are sampled at positions drawn from DUMP_SEED and the array's length alone (ascending), so two
+    runs that compute the same outputs write the same files; all of it stays under 64 MB."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    dev = B.out.device
+
+    def take(t, idx):
+        return t[torch.from_numpy(idx).to(dev)].cpu().numpy()
+
+    rows = _dump_sample(B.n, DUMP_ROWS, rng)
+    offs_idx = rows if len(rows) < B.n else np.arange(B.n + 1, dtype=np.int64)     # (all rows: the end offset too)
+    pos = _dump_sample(int(out_bytes), DUMP_BYTES, rng)
+    sp = _dump_sample(int(n_spans), DUMP_SPANS, rng)
+    spans = B.spans.view(-1, 16)[torch.from_numpy(sp).to(dev)].cpu().numpy()
+    spans = np.ascontiguousarray(spans).view(np.dtype([("utt", "<u4"), ("start", "<u4"), ("end", "<u4"),
+                                                       ("info_type", "<u2"), ("likelihood", "u1"),
+                                                       ("flags", "u1")])).reshape(-1)
+    arrays = {
+        "out_bytes": take(B.out, pos).astype(np.float32),
+        "out_offs": take(B.out_offs, offs_idx).astype(np.float64),
+        "ctx": take(B.ctx, rows).astype(np.float32),
+        "spans": np.stack([spans[f].astype(np.float64) for f in spans.dtype.names], axis=1),
+        "histogram": np.asarray(hist, dtype=np.float64),
+        "totals": np.array([out_bytes, n_spans], dtype=np.float64),
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def reduce_over_ranks(dist, dev, elapsed: float, local_hist: np.ndarray, sums=()):
     """The timed region's cross-rank bookkeeping (the one data collective is the
     histogram all_reduce): max-over-ranks wall time, the SUM of each per-rank quantity in `sums`, the
@@ -399,14 +454,18 @@ def run_rank(args, rank: int, world: int, dev, make_engine, cpu=None, dist=None,
         verified = verified and bool((hist.cpu().numpy() == reduced).all())
     per_stage /= args.steps
     k_ms = {k: v / args.steps for k, v in k_ms.items()}
-    stages = stage_probe(eng, lambda i: step())
+    full = getattr(args, "full", False)
+    if getattr(args, "dump_outputs", None):      # the last timed step's outputs, before any further call
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                     B, ob, ns, local)
+    stages = stage_probe(eng, lambda i: step()) if full else None
     n_pairs, n_events = eng.queue_sizes()
     names = list(eng.type_names)
     eng.close()
     if rank != 0:
         return None
     scan_wall_ms = None
-    if one_stream_probe:         # (after the timed region: per-pass k_scan time for the roofline)
+    if one_stream_probe and full:   # (after the timed region: per-pass k_scan time for the roofline)
         scan_wall_ms = k_ms["k_scan"]
         k_ms["k_scan"] = one_stream_scan_ms(B, make_engine, C)
     n, n_bytes = B.n, B.n_bytes
@@ -446,9 +505,9 @@ def run_rank(args, rank: int, world: int, dev, make_engine, cpu=None, dist=None,
         "utt_per_s": round(n * world * args.steps / elapsed, 1),
         "spans_per_step_per_gpu": int(ns),
         "queues_per_step_per_gpu": {"scan_events": n_events, "candidate_pairs": n_pairs},
-        "stages_ms": {k: round(float(v), 4) for k, v in zip(
+        **({"stages_ms": {k: round(float(v), 4) for k, v in zip(
             ["scan+pairs", "context", "resolve", "offsets", "redact", "pipeline"], stages)},
-        "stages_note": STAGES_NOTE,
+            "stages_note": STAGES_NOTE} if full else {}),
         "kernels_ms": {k: round(v, 4) for k, v in k_ms.items()},
         **({"scan_stage_wall_ms": round(scan_wall_ms, 4),
             "scan_stage_note": "kernels_ms.k_scan and roofline.launch_ms: the SCAN passes' kernel time, from "
@@ -499,7 +558,12 @@ def main():
     ap.add_argument("--bank", type=int, default=16384, help="agent / customer utterance bank size")
     ap.add_argument("--cpu-gb", type=float, default=1.0, help="bytes the CPU baseline times (>= 1 GB, BASELINE.md)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="(config 3 baseline) CPU seconds")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the CPU baseline, the per-stage probe steps after the "
+                         "timed region (stages_ms), config 5's one-stream k_scan pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (scan, long and config5 workloads)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--workload", choices=["scan", "window", "stream", "long", "config5", "ner", "ner-redact",
                                            "service"],
                     default="scan",
@@ -522,6 +586,12 @@ def main():
     ap.add_argument("--stream-weak", action="store_true", help="(config 4) --stream-gb per GPU instead of per node")
     ap.add_argument("--shard-gb", type=float, default=1.0, help="(config 4) host shard each rank replays, GB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload not in ("scan", "long", "config5"):
+        ap.error("--dump-outputs is implemented for the scan, long and config5 workloads")
+    if not args.full:
+        args.no_cpu_baseline = True            # every CPU baseline is a run of its own
     if args.workload == "window":
         return window_main(args)
     if args.workload == "stream":
@@ -1245,7 +1315,8 @@ def window_main(args):
     K = args.steps
     per_stage /= K
     k_red /= K
-    stages = stage_probe(eng, lambda i: step(warm + K + i)) if warm + K + 3 <= U else per_stage
+    probe = args.full and warm + K + 3 <= U
+    stages = stage_probe(eng, lambda i: step(warm + K + i)) if probe else per_stage
     wkey = "window_config5" if c5path else "window"          # (profiles/traffic.json: its own PMC passes)
     # window bytes read to write the outputs: every window's utterances and separators
     lens = (meta.offsets[1:] - meta.offsets[:-1]).astype(np.int64).reshape(U, C)
@@ -1279,7 +1350,7 @@ def window_main(args):
         "stages_ms": {k: round(float(v), 4) for k, v in zip(
             ["scan+pairs", "context", "first+cands", "select+offsets", "redact+commit", "pipeline"], stages)},
         "stages_note": STAGES_NOTE,
-        "probe_steps": 3 if warm + K + 3 <= U else 0,
+        "probe_steps": 3 if probe else 0,
         "pipeline": {"algorithmic_bytes": int(B / K), "GBps": round(B / t_pipe / 1e9, 1),
                      "frac": round(B / t_pipe / 1e9 / HBM_PEAK_GBPS, 4),
                      "traffic": measured_pipeline_traffic(int(meta.offsets[-1]), wkey)},

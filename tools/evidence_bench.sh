@@ -9,7 +9,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 run() {   # name, timeout, bench args...
   local n=$1 t=$2; shift 2
-  timeout -k 10 "$t" python -u bench.py "$@" > "$O/bench_$n.log" 2>&1 || { echo "BENCH $n FAILED"; tail -5 "$O/bench_$n.log"; return 1; }
+  timeout -k 10 "$t" python -u bench.py --full "$@" > "$O/bench_$n.log" 2>&1 || { echo "BENCH $n FAILED"; tail -5 "$O/bench_$n.log"; return 1; }
   grep '^{' "$O/bench_$n.log" | tail -1 > "$O/bench_$n.json"
   python3 -c "import json,sys; b=json.load(open(sys.argv[1])); print(sys.argv[2], b['value'], b['unit'], b['ms_per_step'])" "$O/bench_$n.json" "$n"
 }
