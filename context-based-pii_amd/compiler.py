@@ -678,6 +678,149 @@ def minimize(dfa: DFA) -> DFA:
     return DFA(dfa.cmap, trans, flags, start, accept)
 
 
+# ======================================================================= deidentify_config ====
+# What happens to a finding's bytes (dlp_config.yaml:195-199): per info type, the first transformation
+# that lists it, else the first without info_types, else the bytes stay (DLP leaves findings no
+# transformation names).  The values are the engine's PII_XF_* (include/pii_engine.h).
+XF_INFO_TYPE, XF_REPLACE, XF_REDACT, XF_MASK, XF_KEEP = range(5)
+XF_MASK_WORDS = 8          # per type: char | reverse << 8, number_to_mask, 4 words of skip set, 2 spare
+XF_REPLACE_MAX = 255
+_XF_PRIMITIVES = {"replace_with_info_type_config": XF_INFO_TYPE, "replace_config": XF_REPLACE,
+                  "redact_config": XF_REDACT, "character_mask_config": XF_MASK}
+# every other primitive of DLP's PrimitiveTransformation: named in the error when one is configured
+_XF_UNSUPPORTED = ("crypto_replace_ffx_fpe_config", "crypto_hash_config", "crypto_deterministic_config",
+                   "date_shift_config", "bucketing_config", "fixed_size_bucketing_config", "time_part_config",
+                   "replace_dictionary_config")
+_XF_COMMON = {"NUMERIC": "0123456789", "ALPHA_UPPER_CASE": "ABCDEFGHIJKLMNOPQRSTUVWXYZ",
+              "ALPHA_LOWER_CASE": "abcdefghijklmnopqrstuvwxyz",
+              "PUNCTUATION": "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~", "WHITESPACE": " \t\n\r\x0b\x0c"}
+
+
+@dataclass
+class Transform:
+    kind: int
+    value: bytes = b""         # XF_REPLACE: the replacement
+    mask_char: int = 0x2A      # XF_MASK
+    count: int = 0             # 0 = every character
+    reverse: bool = False
+    skip: int = 0              # 128-bit ASCII set: copied and not counted
+
+
+def _parse_mask(cfg: dict) -> Transform:
+    cfg = cfg or {}
+    unknown = set(cfg) - {"masking_character", "number_to_mask", "reverse_order", "characters_to_ignore"}
+    if unknown:
+        raise RuleError(f"character_mask_config: unsupported field {sorted(unknown)[0]}")
+    ch = cfg.get("masking_character", "*")
+    if not isinstance(ch, str) or len(ch) != 1 or ord(ch) > 127:
+        raise RuleError(f"character_mask_config: masking_character {ch!r} is not one ASCII character")
+    n = cfg.get("number_to_mask", 0) or 0
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0 or n >= 1 << 32:
+        raise RuleError(f"character_mask_config: number_to_mask {n!r} is not a count >= 0")
+    rev = cfg.get("reverse_order", False)
+    if not isinstance(rev, bool):
+        raise RuleError(f"character_mask_config: reverse_order {rev!r} is not true or false")
+    skip = 0
+    for ign in cfg.get("characters_to_ignore", []) or []:
+        if set(ign) - {"characters_to_skip", "common_characters_to_ignore"} or len(ign) != 1:
+            raise RuleError(f"character_mask_config: unsupported characters_to_ignore entry {ign!r}")
+        if "characters_to_skip" in ign:
+            chars = ign["characters_to_skip"]
+            if not isinstance(chars, str) or any(ord(c) > 127 for c in chars):
+                raise RuleError(f"character_mask_config: characters_to_skip {chars!r} is not ASCII")
+        else:
+            cls = ign["common_characters_to_ignore"]
+            if cls not in _XF_COMMON:
+                raise RuleError(f"character_mask_config: unknown common_characters_to_ignore {cls!r}")
+            chars = _XF_COMMON[cls]
+        for c in chars:
+            skip |= 1 << ord(c)
+    return Transform(XF_MASK, mask_char=ord(ch), count=n, reverse=rev, skip=skip)
+
+
+def _parse_primitive(prim: dict) -> Transform:
+    prim = prim or {}
+    if len(prim) != 1:
+        raise RuleError(f"a primitive_transformation holds exactly one primitive, not {sorted(prim)}")
+    (name, cfg), = prim.items()
+    if name not in _XF_PRIMITIVES:
+        known = "unsupported" if name in _XF_UNSUPPORTED else "unknown"
+        raise RuleError(f"{known} primitive transformation {name}")
+    kind = _XF_PRIMITIVES[name]
+    if kind == XF_MASK:
+        return _parse_mask(cfg)
+    if kind == XF_REPLACE:
+        nv = (cfg or {}).get("new_value", {}) or {}
+        if set(nv) != {"string_value"} or not isinstance(nv["string_value"], str):
+            raise RuleError("replace_config: only new_value.string_value is supported")
+        value = nv["string_value"].encode("utf-8")
+        if len(value) > XF_REPLACE_MAX:
+            raise RuleError(f"replace_config: string_value is {len(value)} bytes (more than {XF_REPLACE_MAX})")
+        return Transform(XF_REPLACE, value=value)
+    if cfg:
+        raise RuleError(f"{name}: unsupported field {sorted(cfg)[0]}")
+    return Transform(kind)
+
+
+def parse_deidentify(dlp_config: dict, type_names: Sequence[str]) -> List[Transform]:
+    """deidentify_config -> one Transform per info type (type order).  No block: "[TYPE]" for all."""
+    if "deidentify_config" not in dlp_config or dlp_config["deidentify_config"] is None:
+        return [Transform(XF_INFO_TYPE) for _ in type_names]
+    de = dlp_config["deidentify_config"]
+    for k in de:
+        if k != "info_type_transformations":
+            raise RuleError(f"deidentify_config: {k} is not supported")
+    itt = de.get("info_type_transformations", {}) or {}
+    for k in itt:
+        if k != "transformations":
+            raise RuleError(f"info_type_transformations: {k} is not supported")
+    known = set(type_names)
+    listed: Dict[str, Transform] = {}
+    catch_all: Optional[Transform] = None
+    for entry in itt.get("transformations", []) or []:
+        for k in entry:
+            if k not in ("info_types", "primitive_transformation"):
+                raise RuleError(f"transformation: {k} is not supported")
+        if "primitive_transformation" not in entry:
+            raise RuleError("transformation without a primitive_transformation")
+        tf = _parse_primitive(entry["primitive_transformation"])
+        names = [it.get("name") for it in entry.get("info_types", []) or []]
+        for n in names:
+            if n not in known:
+                raise RuleError(f"deidentify_config names an unknown info type {n}")
+            listed.setdefault(n, tf)
+        if not names and catch_all is None:
+            catch_all = tf
+    default = catch_all if catch_all is not None else Transform(XF_KEEP)
+    return [listed.get(n, default) for n in type_names]
+
+
+def transform_sections(transforms: Sequence[Transform]) -> "OrderedDict[str, np.ndarray]":
+    """The optional xf.* blob sections; none when every type keeps the "[TYPE]" token (the engine's
+    behaviour without them), so such a config compiles to the blob it always did."""
+    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    if all(t.kind == XF_INFO_TYPE for t in transforms):
+        return out
+    T = len(transforms)
+    off = np.zeros(T + 1, dtype=np.uint32)
+    repl = b""
+    mask = np.zeros((T, XF_MASK_WORDS), dtype=np.uint32)
+    for i, t in enumerate(transforms):
+        if t.kind == XF_REPLACE:
+            repl += t.value
+        off[i + 1] = len(repl)
+        if t.kind == XF_MASK:
+            mask[i, 0] = t.mask_char | (0x100 if t.reverse else 0)
+            mask[i, 1] = t.count
+            for w in range(4):
+                mask[i, 2 + w] = (t.skip >> (32 * w)) & 0xFFFFFFFF
+    out["xf.kind"] = np.array([t.kind for t in transforms], dtype=np.uint8)
+    out["xf.repl_off"] = off
+    out["xf.repl"] = np.frombuffer(repl or b"\0", dtype=np.uint8).copy()
+    out["xf.mask"] = mask.reshape(-1)
+    return out
+
+
 # ================================================================================ rule model ====
 @dataclass
 class Pattern:
@@ -760,6 +903,8 @@ class Rules:
         if len(self.type_names) <= PSEUDO_GROUP_MAX_TYPES:
             named = {t for t, _, _ in self.kw_groups} | set(self.external_types)
             self.kw_groups.extend((t, None, False) for t in self.type_names if t not in named)
+
+        self.transforms = parse_deidentify(dlp_config, self.type_names)
 
     @classmethod
     def load(cls, dlp_config_path: Optional[str] = None, builtin_path: Optional[str] = None) -> "Rules":
@@ -1203,6 +1348,8 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
             S[f"scan.g{g}.cmap"] = m.cmap.astype(np.uint8)
             S[f"scan.g{g}.trans"] = m.trans.reshape(-1)
             S[f"scan.g{g}.accid"] = global_accid(g, m)
+    # deidentify_config: per-type kind, replacement strings, mask parameters (absent: "[TYPE]" for all)
+    S.update(transform_sections(rules.transforms))
     blob = _sections_to_blob(S)
     return Compiled(rules, scan_d, scan_k, first, hot, hot_rules, S, blob, [[p.pid for p in ps] for ps, _ in groups])
 

@@ -19,7 +19,9 @@
 //   k_select       finditer skipping, exclusion, overlap resolution, output sizing
 //   k_scan_*       exclusive scans -> output byte offsets and span offsets
 //   k_finalize     capacity / error check (device side)
-//   k_redact       prefix-sum scatter of kept bytes and "[INFO_TYPE]" tokens, span list, histogram
+//   k_redact       prefix-sum scatter of kept bytes and each finding's output (its "[INFO_TYPE]" token, or
+//                  what the rules' deidentify_config says for its type: out_len), span list, histogram
+//   k_mask         character_mask_config: masks the findings k_redact<true> copied (rules with a mask type)
 //   k_ctx_commit   write the per-conversation context back (only when the call succeeded)
 #include <hip/hip_runtime.h>
 
@@ -106,10 +108,24 @@ struct RulesDev {
     const uint16_t* rule_ids;
     const uint32_t* excl_off;    // [V*T+1]
     const uint16_t* excl_ids;
-    const uint32_t* tok_off;     // [T+1] into tok_bytes: "[NAME]"
+    const uint32_t* tok_off;     // [T+1] into tok_bytes: a type's fixed output ("[NAME]", its replace_config
+                                 // string, nothing for redact_config / mask / keep)
     const uint8_t* tok_bytes;
+    const uint32_t* tok_len;     // [T+1] per type: its fixed output length, or XF_SAME_LEN (mask / keep); see out_len
+    const uint8_t* xf_kind;      // [T] PII_XF_*
+    const uint32_t* xf_mask;     // [T*XF_MASK_WORDS] mask types: char | reverse << 8, number_to_mask, 128-bit skip set
     uint32_t nl_off;             // tok_bytes[nl_off] = '\n' (the re-scan window separator)
 };
+
+// Output length of a finding of type t over in_len input bytes (deidentify_config): the token or
+// replacement length of the fixed kinds (0 for redact_config), in_len for character_mask_config and
+// for a type no transformation names.  `tl` is the per-type table (RulesDev::tok_len or its LDS copy).
+constexpr uint32_t XF_SAME_LEN = 0x80000000u;
+constexpr int XF_MASK_WORDS = 8;
+__device__ __forceinline__ uint32_t out_len(const uint32_t* tl, uint32_t t, uint32_t in_len) {
+    const uint32_t l = tl[t];
+    return (l & XF_SAME_LEN) ? in_len : l;
+}
 
 // ------------------------------------------------------------------------------- lane geometry
 // A scan LANE is the set of utterances whose START lies in one slice [c << sh, (c+1) << sh) of the
@@ -2575,7 +2591,7 @@ struct SelTabs {
     uint32_t xw;
     const uint32_t* xloff;
     const uint16_t* xids;
-    const uint32_t* tokoff;
+    const uint32_t* toklen;   // per-type output length table (out_len)
 };
 struct SelIO {
     const uint64_t* lane_pair;
@@ -2617,7 +2633,7 @@ __device__ __forceinline__ SelTabs sel_tabs(const uint8_t* lb, const LdsImage& l
     T.xw = (li.aux >> 3) & 7u;
     T.xloff = reinterpret_cast<const uint32_t*>(lb + li.off[SE_XLOFF]);
     T.xids = reinterpret_cast<const uint16_t*>(lb + li.off[SE_XIDS]);
-    T.tokoff = reinterpret_cast<const uint32_t*>(lb + li.off[SE_TOKOFF]);
+    T.toklen = reinterpret_cast<const uint32_t*>(lb + li.off[SE_TOKOFF]);
     return T;
 }
 
@@ -2696,7 +2712,7 @@ struct LaneSel {
             f.flags = 0;
             fdl[nfl++] = f;
             max_end = best_e;
-            const int d = (int)(Tb.tokoff[best_t + 1] - Tb.tokoff[best_t]) - (best_e - s);
+            const int d = (int)out_len(Tb.toklen, (uint32_t)best_t, (uint32_t)(best_e - s)) - (best_e - s);
             // (selects, not branches: a branch on which counter to add to makes the compiler keep
             // the counters in a scratch array)
             const bool clo_r = cut_lo_row(u), cut_r = cut_row(u);
@@ -3725,7 +3741,7 @@ __global__ __launch_bounds__(256) void k_spans(const RulesDev R, const Geo g, co
         if (act) {
             F = fd[o_fb + k];
             t = F.info_type;
-            d = (int64_t)(R.tok_off[t + 1] - R.tok_off[t]) - (int64_t)(F.end - F.start);
+            d = (int64_t)out_len(R.tok_len, t, F.end - F.start) - (int64_t)(F.end - F.start);
         }
         const uint32_t uk = act ? F.utt : 0xffffffffu;
         // running delta before this finding: its (lane, utterance) run's base + the run's earlier deltas
@@ -3781,12 +3797,14 @@ __global__ __launch_bounds__(256) void k_tile_first(const RulesDev R, const RSpa
         const uint64_t m = (a + b) >> 1;
         const RSpan r = rsp[m];
         const uint32_t t = rs_type(r);
-        if ((int64_t)(rs_out(r) + (R.tok_off[t + 1] - R.tok_off[t])) > lo) b = m;
+        if ((int64_t)(rs_out(r) + out_len(R.tok_len, t, r.in_hi - r.in_lo)) > lo) b = m;
         else a = m + 1;
     }
     tile_first[k] = (uint32_t)a;
 }
 
+// SRC: the rules hold a mask / keep type (a second instantiation; rules without one launch <false>)
+template <bool SRC>
 __global__ __launch_bounds__(REDACT_BLOCK) void k_redact(const RulesDev R, const uint8_t* __restrict__ text,
                                                          const uint64_t* __restrict__ offs,
                                                          const RSpan* __restrict__ rsp,
@@ -3825,20 +3843,24 @@ __global__ __launch_bounds__(REDACT_BLOCK) void k_redact(const RulesDev R, const
         if (mine) {
             const uint32_t ty = rs_type(r);
             const int64_t so = (int64_t)rs_out(r);
-            const int64_t tl = (int64_t)(R.tok_off[ty + 1] - R.tok_off[ty]);
+            const int64_t tl = (int64_t)out_len(R.tok_len, ty, r.in_hi - r.in_lo);
             if (k == 0) {                             // from lo, shifted like the run before span i
                 s_pout[0] = 0;
                 s_psrc[0] = (uint64_t)(uintptr_t)(tb + (lo - (so - (int64_t)r.in_lo)));
             } else {                                  // from the previous token's end
                 const RSpan pr = rsp[j - 1];
                 const uint32_t pt = rs_type(pr);
-                const int64_t pe = (int64_t)rs_out(pr) + (int64_t)(R.tok_off[pt + 1] - R.tok_off[pt]);
+                const int64_t pe = (int64_t)rs_out(pr) + (int64_t)out_len(R.tok_len, pt, pr.in_hi - pr.in_lo);
                 s_pout[2 * k] = (uint32_t)(pe - lo);
                 s_psrc[2 * k] = (uint64_t)(uintptr_t)(tb + pr.in_hi);
             }
             const int64_t ts = max(so, lo);
             s_pout[2 * k + 1] = (uint32_t)(ts - lo);
-            s_psrc[2 * k + 1] = (uint64_t)(uintptr_t)(R.tok_bytes + R.tok_off[ty] + (ts - so));
+            // (SRC: a mask / keep type's output is the finding's own bytes; k_mask then overwrites the
+            // masked ones in place)
+            s_psrc[2 * k + 1] = SRC && (R.tok_len[ty] & XF_SAME_LEN)
+                                    ? (uint64_t)(uintptr_t)(tb + r.in_lo + (ts - so))
+                                    : (uint64_t)(uintptr_t)(R.tok_bytes + R.tok_off[ty] + (ts - so));
             if ((uint32_t)k + 1 == n) {
                 const int64_t te = min(so + tl, hi);
                 s_pout[2 * n] = (uint32_t)(te - lo);
@@ -3860,6 +3882,75 @@ __global__ __launch_bounds__(REDACT_BLOCK) void k_redact(const RulesDev R, const
         __syncthreads();
         i += n;
         lo = hi;
+    }
+}
+
+// character_mask_config, after k_redact<true> has copied a mask type's finding to the output unchanged:
+// one thread per span walks the finding's UTF-8 code points (from the end when reverse_order) and
+// overwrites every byte of a masked code point with the masking character, until number_to_mask code
+// points are masked (0 = all).  A single-byte code point in the type's skip set is kept and not
+// counted.  The output length never depends on the text (out_len), so only bytes inside the span's
+// own output range [rs_out, rs_out + in_len) are written.  Launched only for rules with a mask type.
+__global__ __launch_bounds__(256) void k_mask(const RulesDev R, const uint8_t* __restrict__ text,
+                                              const uint64_t* __restrict__ offs, const RSpan* __restrict__ rsp,
+                                              const uint64_t* __restrict__ n_spans_p,
+                                              const uint32_t* __restrict__ err, uint8_t* __restrict__ out) {
+    if (*err != 0) return;
+    const uint64_t si = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;      // span index
+    if (si >= *n_spans_p) return;
+    const RSpan r = rsp[si];
+    const uint32_t t = rs_type(r);
+    if (R.xf_kind[t] != PII_XF_MASK) return;
+    const uint4 m0 = *reinterpret_cast<const uint4*>(R.xf_mask + (size_t)t * XF_MASK_WORDS);
+    const uint2 m1 = *reinterpret_cast<const uint2*>(R.xf_mask + (size_t)t * XF_MASK_WORDS + 4);
+    const uint8_t mc = (uint8_t)(m0.x & 0xffu);
+    const bool rev = ((m0.x >> 8) & 1u) != 0;
+    const uint32_t limit = m0.y ? m0.y : 0xffffffffu;
+    const uint8_t* in = text + offs[0] + r.in_lo;
+    uint8_t* o = out + rs_out(r);
+    const int len = (int)(r.in_hi - r.in_lo);
+    // The walk as a per-byte state machine, so that the text is read as 16-byte windows (load16: only
+    // aligned chunks that hold a byte of the span) instead of one dependent byte load per step.  A code
+    // point starts at a byte that is not a continuation byte (10xxxxxx); walking backwards, at the byte
+    // after a start.  There the decision for the whole code point is taken: an ASCII byte of the skip
+    // set is kept and not counted, anything else is masked while the count allows.
+    uint32_t masked = 0;
+    bool cur = false;                            // the code point being walked is masked
+    auto step = [&](uint32_t b, int i, bool newcp) -> bool {
+        if (newcp) {
+            if (masked >= limit) return false;
+            const uint32_t sw = b < 32u ? m0.z : b < 64u ? m0.w : b < 96u ? m1.x : m1.y;
+            cur = !(b < 128u && ((sw >> (b & 31u)) & 1u));
+            masked += cur ? 1u : 0u;
+        }
+        if (cur) o[i] = mc;
+        return true;
+    };
+    if (!rev) {
+        for (int j = 0; j < len; j += 16) {
+            const int n = len - j < 16 ? len - j : 16;
+            uint4 w = load16(in + j, 0, n);
+            for (int k = 0; k < n; ++k) {
+                const uint32_t b = w.x & 0xffu;
+                if (!step(b, j + k, (b & 0xC0u) != 0x80u || j + k == 0)) return;
+                shr8(w);
+            }
+        }
+    } else {
+        bool newcp = true;                       // the byte after this one starts a code point (or is the end)
+        for (int j = len; j > 0; j -= 16) {
+            const int w0 = j - 16, klo = w0 < 0 ? -w0 : 0;      // window [w0, j), its bytes klo .. 15 in the span
+            uint4 w = load16(in + w0, klo, 16);
+            for (int k = 15; k >= klo; --k) {
+                const uint32_t b = w.w >> 24;
+                if (!step(b, w0 + k, newcp)) return;
+                newcp = (b & 0xC0u) != 0x80u;
+                w.w = (w.w << 8) | (w.z >> 24);
+                w.z = (w.z << 8) | (w.y >> 24);
+                w.y = (w.y << 8) | (w.x >> 24);
+                w.x <<= 8;
+            }
+        }
     }
 }
 
@@ -4451,7 +4542,7 @@ __global__ __launch_bounds__(256) void k_win_select(const RulesDev R, const uint
     const void* xix = lb + li.off[WS_XOFF];
     const uint32_t* xloff = reinterpret_cast<const uint32_t*>(lb + li.off[WS_XLOFF]);
     const uint16_t* xids = reinterpret_cast<const uint16_t*>(lb + li.off[WS_XIDS]);
-    const uint32_t* tokoff = reinterpret_cast<const uint32_t*>(lb + li.off[WS_TOKOFF]);
+    const uint32_t* toklen = reinterpret_cast<const uint32_t*>(lb + li.off[WS_TOKOFF]);
     const void* rix = lb + li.off[WS_ROFF];
     const uint32_t* rloff = reinterpret_cast<const uint32_t*>(lb + li.off[WS_RLOFF]);
     const uint16_t* rids = reinterpret_cast<const uint16_t*>(lb + li.off[WS_RIDS]);
@@ -4491,7 +4582,7 @@ __global__ __launch_bounds__(256) void k_win_select(const RulesDev R, const uint
                 f.flags = 0;
                 fdu[nf++] = f;
                 max_end = f.end;
-                delta += (int)(tokoff[best_t + 1] - tokoff[best_t]) - (best_e - s);
+                delta += (int)out_len(toklen, (uint32_t)best_t, (uint32_t)(best_e - s)) - (best_e - s);
             }
             best_e = -1;
         };
@@ -4639,7 +4730,8 @@ __device__ uint8_t win_byte_slow(const RulesDev& R, const WinRing& W, const WinB
             const uint32_t run = F[fi].start - pin;
             if (rel < pout + run) return Ej.t[pin - oj + (rel - pout)];
             pout += run;
-            const uint32_t t0 = R.tok_off[F[fi].info_type], tl = R.tok_off[F[fi].info_type + 1] - t0;
+            const uint32_t t0 = R.tok_off[F[fi].info_type];
+            const uint32_t tl = out_len(R.tok_len, F[fi].info_type, F[fi].end - F[fi].start);
             if (rel < pout + tl) return R.tok_bytes[t0 + (rel - pout)];
             pout += tl;
             pin = F[fi].end;
@@ -4720,7 +4812,7 @@ __global__ __launch_bounds__(REDACT_BLOCK) void k_win_redact(const RulesDev R, c
                     s_pout[pb] = po;
                     s_psrc[pb] = (uint64_t)(uintptr_t)(R.tok_bytes + t0);
                     ++pb;
-                    po += R.tok_off[Fi.info_type + 1] - t0;
+                    po += out_len(R.tok_len, Fi.info_type, Fi.end - Fi.start);
                     pin = Fi.end;
                     ++fi;
                 }
@@ -5033,6 +5125,10 @@ struct pii_engine {
     DevImage img_first_hot;            // img_first past LDS: the automata of its first first_p_hot patterns
     uint32_t first_p_hot = 0;
     bool lists_cl = false;
+    // deidentify_config (optional xf.* blob sections): per-type PII_XF_*; any mask / keep type (k_redact<true>,
+    // the FULL window re-scan), any mask type (k_mask)
+    std::vector<uint8_t> xf_kind;
+    bool xf_src = false, xf_mask = false;
     hipStream_t aux[2] = {nullptr, nullptr};   // more streams for the SCAN groups' passes (PII_SCAN_STREAMS)
     uint32_t n_aux = 0;
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};             // the images' rule / exclusion lists are deduplicated (list_range)
@@ -5699,8 +5795,14 @@ int run_pipeline(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                                                               (uint32_t)((uintptr_t)out & 15), tiles, e->d_err,
                                                               e->tile_first);
             if (e->timing >= 1) HIPCHK(hipEventRecord(e->kev[2], st));
-            k_redact<<<tiles, REDACT_BLOCK, 0, st>>>(R, text, offs, e->rsp, e->lane_sp + n_chunks, out_offs + n_utt,
-                                                     total_bytes, e->tile_first, e->d_err, out);
+            (e->xf_src ? k_redact<true> : k_redact<false>)<<<tiles, REDACT_BLOCK, 0, st>>>(
+                R, text, offs, e->rsp, e->lane_sp + n_chunks, out_offs + n_utt, total_bytes, e->tile_first, e->d_err,
+                out);
+            if (e->xf_mask) {   // (a lane's findings arena holds one span per min_len bytes; no more than span_cap)
+                const uint64_t ms = std::min<uint64_t>(span_cap, total_bytes / (uint64_t)Rsel.min_len + n_chunks);
+                k_mask<<<(uint32_t)(ms / 256) + 1, 256, 0, st>>>(R, text, offs, e->rsp, e->lane_sp + n_chunks, e->d_err,
+                                                                 out);
+            }
             if (e->timing >= 1) HIPCHK(hipEventRecord(e->kev[3], st));
             if (!wf)        // (window findings are not counted, as on the incremental window path)
                 k_hist_reduce<<<dim3(e->hist_types, std::max(1u, std::min(32u, nsb / 256))), 256, 0, st>>>(
@@ -6145,11 +6247,44 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
         if (ne > NE_MAX) return fail("too many excluder patterns");
         R.NE = ne;
     }
-    std::vector<uint32_t> tok_off(R.T + 1, 0);
+    // deidentify_config: without the sections every type is replaced by its "[NAME]" token
+    e->xf_kind.assign(R.T, (uint8_t)PII_XF_INFO_TYPE);
+    std::vector<uint32_t> xf_maskp((size_t)std::max(R.T, 1) * XF_MASK_WORDS, 0u);
+    const Section* xs_repl_off = nullptr;
+    const Section* xs_repl = nullptr;
+    if (const Section* xk = find("xf.kind")) {
+        xs_repl_off = find("xf.repl_off");
+        xs_repl = find("xf.repl");
+        const Section* xm = find("xf.mask");
+        if (xk->bytes != (size_t)R.T || !xs_repl_off || !xs_repl || !xm || xs_repl_off->bytes != ((size_t)R.T + 1) * 4 ||
+            xm->bytes != (size_t)R.T * XF_MASK_WORDS * 4)
+            return fail("transformation tables malformed");
+        const uint32_t* ro = reinterpret_cast<const uint32_t*>(xs_repl_off->data);
+        for (int t = 0; t < R.T; ++t) {
+            if (xk->data[t] > PII_XF_KEEP || ro[t] > ro[t + 1] || ro[t + 1] > xs_repl->bytes || ro[t + 1] - ro[t] > 255)
+                return fail("transformation tables malformed");
+            e->xf_kind[t] = xk->data[t];
+            e->xf_src |= xk->data[t] == PII_XF_MASK || xk->data[t] == PII_XF_KEEP;
+            e->xf_mask |= xk->data[t] == PII_XF_MASK;
+        }
+        std::memcpy(xf_maskp.data(), xm->data, xm->bytes);
+        for (int t = 0; t < R.T; ++t)
+            if (e->xf_kind[t] == PII_XF_MASK && (xf_maskp[(size_t)t * XF_MASK_WORDS] & 0xffu) > 127u)
+                return fail("transformation tables malformed");
+    }
+    // tok_len: the per-type output length table behind out_len (T + 1 entries, as the offsets it replaces
+    // in the k_select / k_win_select images)
+    std::vector<uint32_t> tok_off(R.T + 1, 0), tok_len(R.T + 1, 0);
     std::string tok;
     for (int t = 0; t < R.T; ++t) {
-        tok += "[" + e->names[t] + "]";
+        if (e->xf_kind[t] == PII_XF_INFO_TYPE) {
+            tok += "[" + e->names[t] + "]";
+        } else if (e->xf_kind[t] == PII_XF_REPLACE) {
+            const uint32_t* ro = reinterpret_cast<const uint32_t*>(xs_repl_off->data);
+            tok.append(reinterpret_cast<const char*>(xs_repl->data) + ro[t], ro[t + 1] - ro[t]);
+        }
         tok_off[t + 1] = (uint32_t)tok.size();
+        tok_len[t] = e->xf_kind[t] >= PII_XF_MASK ? XF_SAME_LEN : tok_off[t + 1] - tok_off[t];
     }
     tok += "\n";               // the re-scan window separator (k_win_redact piece source)
     R.nl_off = (uint32_t)tok.size() - 1;
@@ -6238,7 +6373,8 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
            i_hd = addsec("hot.dfa_desc"), i_ve = addsec("var.enabled"), i_vm = addsec("var.minlik"),
            i_ro = addsec("var.rule_off"), i_ri = addsec("var.rule_ids"), i_eo = addsec("var.excl_off"),
            i_ei = addsec("var.excl_ids"), i_to = add(tok_off.data(), tok_off.size() * 4),
-           i_tb = add(tok.data(), tok.size());
+           i_tb = add(tok.data(), tok.size()), i_tl = add(tok_len.data(), tok_len.size() * 4),
+           i_xk = add(e->xf_kind.data(), e->xf_kind.size()), i_xm = add(xf_maskp.data(), xf_maskp.size() * 4);
     struct GroupPut { size_t cmap, td, tk, dacc, kacc, npair; };
     std::vector<GroupPut> gp;
     for (auto& h : hg)
@@ -6277,6 +6413,9 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
     R.excl_ids = (const uint16_t*)at(i_ei);
     R.tok_off = (const uint32_t*)at(i_to);
     R.tok_bytes = (const uint8_t*)at(i_tb);
+    R.tok_len = (const uint32_t*)at(i_tl);
+    R.xf_kind = (const uint8_t*)at(i_xk);
+    R.xf_mask = (const uint32_t*)at(i_xm);
     if (R.n_dacc >= 65535) return fail("too many SCAN accept sets");
     {   // per-kernel LDS images
         auto sec = [&](const char* nm) { return std::make_pair((const void*)find(nm)->data, (size_t)find(nm)->bytes); };
@@ -6337,7 +6476,7 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
         pw[WS_XOFF] = vec(xl.ix);
         pw[WS_XLOFF] = vec(xl.loff);
         pw[WS_XIDS] = vec(xl.ids);
-        pw[WS_TOKOFF] = std::make_pair((const void*)tok_off.data(), tok_off.size() * 4);
+        pw[WS_TOKOFF] = std::make_pair((const void*)tok_len.data(), tok_len.size() * 4);
         pw[WS_ROFF] = vec(rl.ix);
         pw[WS_RLOFF] = vec(rl.loff);
         pw[WS_RIDS] = vec(rl.ids);
@@ -6350,7 +6489,7 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
         ps[SE_XOFF] = vec(xl.ix);
         ps[SE_XLOFF] = vec(xl.loff);
         ps[SE_XIDS] = vec(xl.ids);
-        ps[SE_TOKOFF] = std::make_pair((const void*)tok_off.data(), tok_off.size() * 4);
+        ps[SE_TOKOFF] = std::make_pair((const void*)tok_len.data(), tok_len.size() * 4);
         if (!make_image(pf, e->img_first) || !make_image(pe, e->img_eval) || !make_image(ps, e->img_sel))
             return fail("rule table upload failed");
         e->img_eval.li.aux = aux;
@@ -6636,6 +6775,11 @@ int pii_type_name(pii_engine* e, uint32_t t, char* buf, size_t cap) {
         buf[n] = 0;
     }
     return (int)s.size();
+}
+
+int pii_type_transform(pii_engine* e, uint32_t t) {
+    if (!e || t >= e->xf_kind.size()) return PII_E_ARG;
+    return e->xf_kind[t];
 }
 
 int pii_context_group_type(pii_engine* e, uint32_t g) {
@@ -6998,7 +7142,9 @@ int pii_window_enable_ex(pii_engine* e, uint32_t window_n, uint32_t slot_bytes, 
     // (config 5: the groups' merged pair queue, candidate lists past LIVE patterns spilled like
     // k_select's) and tables past LDS (read in place); any other rule set re-scans the joined windows
     // in full
-    e->win_full = (flags & PII_WINDOW_FULL) || !e->window_ok;
+    // (a mask / keep type's output comes from the text: the window redaction kernel's pieces do not
+    // produce it, the scan+redact pipeline the full re-scan runs does)
+    e->win_full = (flags & PII_WINDOW_FULL) || !e->window_ok || e->xf_src;
     e->win_n = window_n;
     e->win_slot_bytes = slot_bytes;
     return PII_OK;

@@ -28,8 +28,10 @@ EXPORTS = ["pii_engine_create", "pii_engine_destroy", "pii_engine_info", "pii_ty
            "pii_window_count", "pii_rescan_window", "pii_rescan_window_device",
            "pii_rescan_window_device_ex", "pii_scan_redact_ext", "pii_scan_redact_device_ext", "pii_window_enable_ex",
            "pii_window_mode", "pii_set_scratch_limit", "pii_scratch_bytes", "pii_context_resize",
-           "pii_context_update", "pii_set_timing"]
+           "pii_context_update", "pii_set_timing", "pii_type_transform"]
 PII_WINDOW_FULL = 1
+# pii_type_transform: what the rules' deidentify_config does with a finding of a type
+PII_XF_INFO_TYPE, PII_XF_REPLACE, PII_XF_REDACT, PII_XF_MASK, PII_XF_KEEP = range(5)
 
 
 class PiiError(RuntimeError):
@@ -79,6 +81,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.pii_engine_info.argtypes = [P, c.POINTER(pii_info)]
     lib.pii_type_name.argtypes = [P, c.c_uint32, c.c_char_p, c.c_size_t]
     lib.pii_context_group_type.argtypes = [P, c.c_uint32]
+    lib.pii_type_transform.argtypes = [P, c.c_uint32]
     lib.pii_last_error.argtypes = [P]
     lib.pii_last_error.restype = c.c_char_p
     lib.pii_scan_redact.argtypes = [P, P, P, c.c_uint32, P, P, P, P, c.c_uint64, P, P, c.c_uint32,
@@ -189,6 +192,13 @@ class Engine:
         buf = ctypes.create_string_buffer(128)
         self.lib.pii_type_name(self.h, t, buf, 128)
         return buf.value.decode()
+
+    def type_transform(self, t: int) -> int:
+        """PII_XF_* of info type t (pii_type_transform): the rules' deidentify_config, resolved per type"""
+        rc = self.lib.pii_type_transform(self.h, int(t))
+        if rc < 0:
+            raise self._err(rc, "pii_type_transform")
+        return rc
 
     def close(self):
         if getattr(self, "h", None):

@@ -265,10 +265,16 @@ class PiiService:
 
     def __init__(self, engine: Optional[Engine] = None, n_slots: int = 1 << 16,
                  ttl_seconds: int = CONTEXT_TTL_SECONDS, clock: Callable[[], float] = time.time, device: int = 0,
-                 time_base: str = "wall", ner=None, ner_max_len: int = 64, max_slots: Optional[int] = None):
+                 time_base: str = "wall", ner=None, ner_max_len: int = 64, max_slots: Optional[int] = None,
+                 dlp_config_path: Optional[str] = None):
         if time_base not in ("wall", "payload"):
             raise ValueError("time_base must be 'wall' or 'payload'")
-        self.engine = engine if engine is not None else Engine.from_rules(device=device, n_conv_slots=n_slots,
+        # dlp_config_path: the DLP config to compile (its inspect_config, context_keywords and
+        # deidentify_config -- mask / replace / remove per info type); None = the shipped rules
+        if engine is not None and dlp_config_path is not None:
+            raise ValueError("pass an engine or a dlp_config_path to build one from, not both")
+        self.engine = engine if engine is not None else Engine.from_rules(dlp_config_path, device=device,
+                                                                          n_conv_slots=n_slots,
                                                                           ttl_seconds=ttl_seconds)
         self.ttl_us = int(ttl_seconds) * 1_000_000
         self.clock = clock
