@@ -638,6 +638,119 @@ def build_first_dfa(nfa: NFA, start: int, max_states: int = 60000) -> DFA:
     return minimize(dfa)
 
 
+# ------------------------------------------------------------------- absorbed match starts ------
+# A pattern  X{lo,} . rest  whose head is a greedy, unbounded repeat of ONE character class matches at
+# s - 1 whenever it matches at s and text[s-1] is in X, with the same end (the head backtracks through
+# the same positions), so finditer skips the start s as inside the previous match -- unless an earlier
+# match of the pattern ends exactly at s, where finditer resumes.  A match can end at s only if
+# text[s-1] is in Z (the bytes a match can end with) and text[s] is not in G (the class of a trailing
+# greedy unbounded repeat, which would have taken it).  So the start s > 0 is dropped, before its
+# FIRST run, iff
+#     text[s-1] in X  and not (text[s-1] in Z and text[s] not in G)
+# ("absorbed match starts").  Z may be a superset and G a subset: both only keep more.
+_CLASS_OPS = (C.LITERAL, C.NOT_LITERAL, C.ANY, C.IN)
+
+
+def _unbounded_class_repeat(op, av, flags) -> Optional[int]:
+    """The class of a greedy `class{lo,}` item, else None."""
+    if op != C.MAX_REPEAT or av[1] != C.MAXREPEAT:
+        return None
+    sub = list(av[2])
+    if len(sub) != 1 or sub[0][0] not in _CLASS_OPS:
+        return None
+    return Emitter(None, False).charset(sub[0][0], sub[0][1], flags)
+
+
+def _last_bytes(items, flags) -> int:
+    """Superset of the bytes a non-empty match of the sequence `items` can end with."""
+    cs = 0
+    for op, av in reversed(list(items)):
+        if op in _CLASS_OPS:
+            cs |= Emitter(None, False).charset(op, av, flags)
+        elif op == C.AT:
+            pass
+        elif op == C.SUBPATTERN:
+            _group, add_f, del_f, sub = av
+            cs |= _last_bytes(sub, (flags | add_f) & ~del_f)
+        elif op == C.BRANCH:
+            for b in av[1]:
+                cs |= _last_bytes(b, flags)
+        elif op in (C.MAX_REPEAT, C.MIN_REPEAT):
+            cs |= _last_bytes(av[2], flags)
+        else:
+            return ALL
+        if not _nullable(op, av):
+            break
+    return cs
+
+
+def first_drop_sets(pattern) -> Optional[Tuple[int, int, int]]:
+    """(X, Z, G) as byte sets when `pattern` is a top-level sequence that begins with a greedy,
+    unbounded repeat of one character class (no assertion before it); None when not eligible."""
+    tree = parse(pattern)
+    items = list(tree)
+    flags = tree.state.flags
+    if not items:
+        return None
+    x = _unbounded_class_repeat(items[0][0], items[0][1], flags)
+    if not x:
+        return None
+    g = _unbounded_class_repeat(items[-1][0], items[-1][1], flags) or 0
+    return x, _last_bytes(items, flags), g
+
+
+def first_drop(sets: Tuple[int, int, int], prev: int, cur: int) -> bool:
+    """The rule above for one start: `prev` = text[s-1], `cur` = text[s] (s > 0)."""
+    x, z, g = sets
+    return bool((x >> prev) & 1) and not ((z >> prev) & 1 and not (g >> cur) & 1)
+
+
+def drop_start(sets: Optional[Tuple[int, int, int]], text: bytes, s: int) -> bool:
+    """Whether the start s of text is dropped (s == 0 and patterns that are not eligible: never)."""
+    return sets is not None and 0 < s < len(text) and first_drop(sets, text[s - 1], text[s])
+
+
+def add_first_drop(dfa: DFA, sets: Tuple[int, int, int]) -> Tuple[DFA, int]:
+    """The rule as extra states of a FIRST DFA: a PRE state whose row maps the class of text[s-1] to
+    the state the run from s starts in -- the ordinary start of that byte's kind, a dead (terminal)
+    state for a dropped start, or a copy of the start that dies on a byte of G.  Returns the DFA and
+    PRE's index; the states already there keep their numbers."""
+    x, z, g = sets
+    n, ncls = dfa.n_states, dfa.n_classes
+    reps = [int(np.flatnonzero(dfa.cmap == c)[0]) for c in range(ncls)]
+    for cs in (x, z, g):                         # the partition respects every CHAR set of the pattern
+        for c in range(ncls):
+            inside = [(cs >> int(b)) & 1 for b in np.flatnonzero(dfa.cmap == c)]
+            assert min(inside) == max(inside)
+    rows = [list(r) for r in dfa.trans.astype(np.int64)]
+    flags = list(dfa.flags)
+    dead = next((i for i in range(n) if flags[i] == 2 and all(t == i for t in rows[i])), -1)
+    if dead < 0:
+        dead = len(rows)
+        rows.append([dead] * (ncls + 1))
+        flags.append(2)
+    die_g: Dict[int, int] = {}
+    pre_row = []
+    for c, r in enumerate(reps):
+        start = dfa.start[_kind_of_byte(r)]
+        if not (x >> r) & 1 or ((z >> r) & 1 and not g):
+            pre_row.append(start)
+        elif not (z >> r) & 1:
+            pre_row.append(dead)
+        else:
+            if start not in die_g:
+                die_g[start] = len(rows)
+                rows.append([dead if c2 < ncls and (g >> reps[c2]) & 1 else t for c2, t in enumerate(rows[start])])
+                flags.append(flags[start])
+            pre_row.append(die_g[start])
+    pre = len(rows)
+    rows.append(pre_row + [dead])
+    flags.append(0)
+    if len(rows) > 65535:
+        raise RuleError("DFA too large for 16-bit state ids")
+    return DFA(dfa.cmap, np.array(rows, dtype=np.uint16), np.array(flags, dtype=np.uint8), dfa.start, []), pre
+
+
 def minimize(dfa: DFA) -> DFA:
     """Moore partition refinement; initial blocks split by (flags, accept set)."""
     S = dfa.n_states
@@ -1176,10 +1289,16 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
     # the "\n" that joins a re-scan window, and a match inside one utterance is the same
     # match inside the window, which is what lets the engine re-scan windows incrementally.
     window_ok = 1
+    # first_pre: per pattern, the PRE state of add_first_drop (absorbed match starts), -1 = none
+    first_pre = np.full(P, -1, dtype=np.int32)
     for p in rules.patterns:
         n2 = NFA()
         st = add_pattern(n2, p.pattern, p.pid, reverse=False)
-        first.append(build_first_dfa(n2, st))
+        d = build_first_dfa(n2, st)
+        sets = first_drop_sets(p.pattern)
+        if sets is not None:
+            d, first_pre[p.pid] = add_first_drop(d, sets)
+        first.append(d)
         min_len = min(min_len, _min_len(parse(p.pattern)))
         for k, b, cs in zip(n2.kind, n2.b, n2.cs):
             if (k == CHAR and cs & NEWLINE) or (k == ASSERT and b in (A_BEGIN, A_END)):
@@ -1326,6 +1445,7 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
     S["det.lik"] = np.array([p.likelihood for p in rules.patterns], dtype=np.uint8)
     S["det.exidx"] = exidx
     S["det.first_desc"] = first_desc.reshape(-1)
+    S["det.first_pre"] = first_pre
     S["hot.rule"] = hot_desc.reshape(-1)
     S["hot.dfa_desc"] = hot_dfa_desc.reshape(-1)
     S["pool.trans"] = np.concatenate(pool_trans).astype(np.uint16) if pool_trans else np.zeros(1, np.uint16)

@@ -332,6 +332,7 @@ __device__ inline bool validate(int id, const uint8_t* q, int n) {
 
 // ---------------------------------------------------------------------------------- DFA runners
 // descriptor layout (compiler.put): tr_off, fl_off, cm_off, ncols, start_bot, start_w, start_n, n_states
+// (in the kernels' images word 1 is instead a FIRST automaton's PRE state + 1, 0 = none: first_begin)
 // In the kernels' LDS images every transition entry is  next_state | flags(next_state) << 14
 // (FIRST: bit 14 = a match ended before the byte just consumed, bit 15 = terminal; HOT: bit 14 =
 // accept), so one step is two dependent LDS reads (byte class, transition).
@@ -428,7 +429,17 @@ __device__ __forceinline__ int first_begin(const Pool& pool, const int32_t* d, c
     if (s == 0) {
         st = (uint32_t)d[4];
     } else {
-        st = (uint32_t)(is_word(w.x & 0xffu) ? d[5] : d[6]);
+        const uint32_t pc = w.x & 0xffu;
+        const uint32_t pre = (uint32_t)d[1];
+        if (pre) {
+            // absorbed match starts (compiler.add_first_drop): the PRE row maps the class of the byte
+            // before s to the start state; a terminal entry is a start that finditer always skips
+            const uint32_t e = tr[(pre - 1) * nc + cm[pc]];
+            if (e & 0x8000u) return -1;
+            st = e & DFA_STATE_MASK;
+        } else {
+            st = (uint32_t)(is_word(pc) ? d[5] : d[6]);
+        }
         shr8(w);
     }
     int last = -1;

@@ -4967,7 +4967,9 @@ struct DfaPool {
     std::vector<uint8_t> cmap;
     std::vector<int32_t> desc;
 };
-bool add_dfa(DfaPool& dp, const int32_t* d, const uint16_t* trans, const uint8_t* flags, const uint8_t* cmap) {
+// pre: a FIRST automaton's PRE state (absorbed match starts, first_begin), -1 = none
+bool add_dfa(DfaPool& dp, const int32_t* d, const uint16_t* trans, const uint8_t* flags, const uint8_t* cmap,
+             int32_t pre = -1) {
     const int32_t nc = d[3], ns = d[7];
     if (ns > (int32_t)DFA_STATE_MASK + 1) return false;
     int32_t nd[8];
@@ -4978,7 +4980,7 @@ bool add_dfa(DfaPool& dp, const int32_t* d, const uint16_t* trans, const uint8_t
     const size_t k = dp.desc.size() / 8;
     while (dp.trans.size() % 64 != (2 * k) % 64) dp.trans.push_back(0);
     nd[0] = (int32_t)dp.trans.size();
-    nd[1] = 0;
+    nd[1] = pre < 0 ? 0 : pre + 1;
     nd[2] = (int32_t)dp.cmap.size();
     for (size_t i = 0; i < (size_t)ns * nc; ++i) {
         const uint16_t dst = trans[d[0] + i];
@@ -6424,8 +6426,16 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
         const uint8_t* pcmap = (const uint8_t*)find("pool.cmap")->data;
         DfaPool fp, hp;
         const int32_t* fdesc = (const int32_t*)find("det.first_desc")->data;
+        // absorbed match starts: the patterns' PRE states (absent in older blobs: nothing is dropped);
+        // PII_FIRST_DROP=0 turns the drop off
+        const Section* s_pre = find("det.first_pre");
+        if (s_pre && s_pre->bytes < (size_t)R.P * 4) return fail("det.first_pre is too short");
+        if (const char* v = std::getenv("PII_FIRST_DROP"); v && std::atoi(v) == 0) s_pre = nullptr;
+        auto fpre = [&](int p) { return s_pre ? reinterpret_cast<const int32_t*>(s_pre->data)[p] : -1; };
+        for (int p = 0; p < R.P; ++p)
+            if (fpre(p) >= fdesc[8 * p + 7]) return fail("det.first_pre names a state past its automaton");
         bool fits = true;
-        for (int p = 0; p < R.P; ++p) fits &= add_dfa(fp, fdesc + 8 * p, ptrans, pflags, pcmap);
+        for (int p = 0; p < R.P; ++p) fits &= add_dfa(fp, fdesc + 8 * p, ptrans, pflags, pcmap, fpre(p));
         const int32_t* hdesc = (const int32_t*)find("hot.dfa_desc")->data;
         for (int h = 0; h < R.n_hot; ++h) fits &= add_dfa(hp, hdesc + 8 * h, ptrans, pflags, pcmap);
         if (!fits) return fail("a FIRST/HOT automaton has more than 16384 states");
@@ -6534,7 +6544,7 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
                         hf.desc.insert(hf.desc.end(), 8, 0);          // columns 0: not resident
                         continue;
                     }
-                    add_dfa(hf, d, ptrans, pflags, pcmap);
+                    add_dfa(hf, d, ptrans, pflags, pcmap, fpre((int)p));
                 }
                 std::vector<std::pair<const void*, size_t>> ph_parts(FI_N);
                 ph_parts[FI_TRANS] = vec(hf.trans);

@@ -1,4 +1,6 @@
-"""Sparse-stage statistics of the bench corpus (events, pairs, FIRST matches per pattern) via tablesim."""
+"""Sparse-stage statistics of the bench corpus (events, pairs, FIRST matches per pattern) via tablesim,
+and per pattern the matched starts the absorbed-start rule keeps and drops before their FIRST run
+(compiler.drop_start: the compiler's own predicate)."""
 import collections
 import importlib
 import os
@@ -20,6 +22,8 @@ data = synth.gather_bytes(meta, bank)
 o = meta.offsets
 pairs = collections.Counter()
 matched = collections.Counter()
+dropped = collections.Counter()          # matched starts the rule drops (finditer always skips them)
+drop_sets = [compiler.first_drop_sets(p.pattern) for p in comp.rules.patterns]
 ev_n = 0
 steps = 0
 for i in range(meta.n):
@@ -36,8 +40,12 @@ for i in range(meta.n):
             e = sim.first_run(p, t, pos)
             if e >= 0:
                 matched[p] += 1
+                if compiler.drop_start(drop_sets[p], t, pos):
+                    dropped[p] += 1
 names = [comp.rules.patterns[p].type_name for p in range(sim.P)]
 print(f"utterances {meta.n}  D events/utt {ev_n / meta.n:.3f}  pairs/utt {sum(pairs.values()) / meta.n:.3f}  "
-      f"matched/utt {sum(matched.values()) / meta.n:.3f}")
+      f"matched/utt {sum(matched.values()) / meta.n:.3f}  "
+      f"matched kept/utt {(sum(matched.values()) - sum(dropped.values())) / meta.n:.3f}")
 for p in sorted(pairs, key=lambda p: -pairs[p]):
-    print(f"  {p:3d} {names[p]:28s} pairs/utt {pairs[p] / meta.n:.3f} matched/utt {matched[p] / meta.n:.3f}")
+    rule = (f" kept {matched[p] - dropped[p]} dropped {dropped[p]}" if drop_sets[p] is not None else "")
+    print(f"  {p:3d} {names[p]:28s} pairs/utt {pairs[p] / meta.n:.3f} matched/utt {matched[p] / meta.n:.3f}{rule}")
