@@ -89,6 +89,7 @@ struct RulesDev {
                               //   | the next row's end-of-text transition accepts (bit 1)
     const uint16_t* tk;       // [SK*CKs]
     const uint16_t* d_accid;  // [SD*CDs]
+    const uint32_t* d_na;     // [SD*CDs] d_npair | d_accid << 16 (the pair write pass: one gather for both)
     const uint32_t* d_acc_off;
     const uint16_t* d_acc_ids;
     const uint16_t* k_accid;  // [SK*CKs]
@@ -690,6 +691,31 @@ __device__ __forceinline__ void scan_emit(Event* __restrict__ ev, uint32_t ab, u
     }
 }
 
+// The lane's (start, pattern) pair count, summed where its events are born (lane_np, the pair queue's
+// layout key: the count pass k_pairs_flat<false> re-read every event from HBM for this sum).  Called
+// after the scan loop by the thread that wrote the events (program order; k_scan2 moves its B events the
+// same way): no accumulator is held across the loop (summing in scan_emit would cost a VGPR there, and
+// k_scan sits at its 80-VGPR budget), and the re-reads hit the lines the thread just stored.  An empty
+// lane counts 0.
+__device__ __forceinline__ uint32_t lane_pairs(const RulesDev& R, const Event* ev, uint32_t ab, uint32_t cnt) {
+    // eight events per round, their loads issued together and then their counts' (clamped to the lane's
+    // last event, so every load is one of its own records) instead of one event after the other, each
+    // with its dependent table load: the tail costs k_scan 31 us at config 2, 38 in the serial form
+    // (a workgroup keeps its LDS until its last wavefront has waited for its stores and these loads)
+    uint32_t np = 0;
+    for (uint32_t k = 0; k < cnt; k += 8) {
+        uint32_t sd[8];
+#pragma unroll
+        for (uint32_t r = 0; r < 8; ++r) sd[r] = ev[ab + min(k + r, cnt - 1u)].sd;
+#pragma unroll
+        for (uint32_t r = 0; r < 8; ++r) {
+            const uint32_t n = R.d_npair[sd[r]];
+            np += k + r < cnt ? n : 0u;
+        }
+    }
+    return np;
+}
+
 // the group mask for utterance-start bits sb (bit j: byte j starts one): every accept bit (even bits),
 // and the end-of-text bit 2 (7 - j) + 1 of each starting byte j (the m layout of SCAN_STEP8)
 __device__ __forceinline__ uint32_t scan_spread(uint32_t sb) {
@@ -825,7 +851,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == SCAN_B
                                                      const uint64_t* __restrict__ words,
                                                      const uint32_t* __restrict__ lane_perm, Event* __restrict__ ev,
                                                      uint32_t* __restrict__ lane_cnt, uint32_t* __restrict__ lane_st,
-                                                     const uint32_t* __restrict__ err, uint32_t ilv) {
+                                                     const uint32_t* __restrict__ err, uint32_t ilv,
+                                                     uint32_t* __restrict__ lane_np) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem32[];
     if (*err & ERR_ARGS) return;              // the declared batch size was wrong: nothing is sized for it
     // LDS: class map at 0 (256 x class words: D base + 2 classD | (K base + 2 classK) << 16), D table,
@@ -919,6 +946,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == SCAN_B
         if (L.clo) lane_st[2 * c + 1] = scan_state(nd, nk);        // lo is block aligned: state after byte lo
     }
     lane_cnt[c] = cnt;
+    if (lane_np) lane_np[c] = lane_pairs(R, ev, (uint32_t)ev_base(L, c), cnt);
 }
 
 // ------------------------------------------------------------------ k_scan2: two chains per lane
@@ -1099,7 +1127,8 @@ template <bool HK, int NT = SCAN2_BLOCK>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == SCAN2_BLOCK ? SCAN2_WAVES : 4, NT == SCAN2_BLOCK ? SCAN2_WAVES : 4))) void k_scan2(
     const RulesDev R, const Geo g, const uint8_t* __restrict__ text, const uint32_t* __restrict__ words,
     const uint32_t* __restrict__ split, const uint32_t* __restrict__ lane_perm, Event* __restrict__ ev,
-    uint32_t* __restrict__ lane_cnt, uint32_t* __restrict__ lane_st, const uint32_t* __restrict__ err) {
+    uint32_t* __restrict__ lane_cnt, uint32_t* __restrict__ lane_st, const uint32_t* __restrict__ err,
+    uint32_t* __restrict__ lane_np) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem32[];
     if (*err & ERR_ARGS) return;
     const int nd_words = R.SD * R.CDs / 2;
@@ -1213,6 +1242,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == SCAN2_
         cnt = cntA + cntB;
     }
     lane_cnt[lane_perm[t]] = cnt;
+    // (B's events sit behind A's by now: the arena holds the lane's cnt events from its base)
+    if (lane_np) lane_np[lane_perm[t]] = lane_pairs(R, ev, (uint32_t)ev_base(g_lane(g, lane_perm[t]), lane_perm[t]), cnt);
 }
 
 // ---- k_scan_fix: stitching of cut rows.  A lane cut at hi scanned SCAN_HALO bytes past the cut from
@@ -1223,7 +1254,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == SCAN2_
 // a re-scanned lane until nothing changes.  Re-scans are rare and sequential per lane.
 __device__ void rescan_lane(const RulesDev& R, const Geo& g, const uint8_t* __restrict__ text, uint32_t c,
                             uint32_t entry, Event* __restrict__ ev, uint32_t* __restrict__ lane_cnt,
-                            uint32_t* __restrict__ lane_st) {
+                            uint32_t* __restrict__ lane_st, uint32_t* __restrict__ lane_np) {
     const uint32_t* s_cmap = nullptr;        // LDS address 0 (k_scan layout)
     (void)s_cmap;
     const Lane L = g_lane(g, c);
@@ -1260,6 +1291,7 @@ __device__ void rescan_lane(const RulesDev& R, const Geo& g, const uint8_t* __re
         }
     }
     lane_cnt[c] = cnt;
+    if (lane_np) lane_np[c] = lane_pairs(R, ev, ab, cnt);       // the lane's events changed: so did its pairs
     lane_st[2 * c] = entry;
     if (L.clo) lane_st[2 * c + 1] = scan_state(nd, nk);
 }
@@ -1286,7 +1318,7 @@ __global__ __launch_bounds__(256) void k_scan_fix(const RulesDev* __restrict__ R
                                                   const uint32_t* __restrict__ long_count, Event* __restrict__ ev0,
                                                   uint64_t ev_stride, uint32_t* __restrict__ cnt0,
                                                   uint32_t* __restrict__ st0, uint64_t lane_stride,
-                                                  uint32_t* __restrict__ err) {
+                                                  uint32_t* __restrict__ err, uint32_t* __restrict__ lane_np) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem32[];
     if (blockIdx.x >= *long_count) return;
     const RulesDev R = Rs[blockIdx.y];
@@ -1371,7 +1403,7 @@ __global__ __launch_bounds__(256) void k_scan_fix(const RulesDev* __restrict__ R
             if (n == 0 && !s_full) break;
             if (!staged) stage();                       // (n and s_full are block-uniform here)
             for (uint32_t k = threadIdx.x; k < n; k += blockDim.x)
-                rescan_lane(R, g, text, s_q[k], s_e[k], ev, lane_cnt, lane_st);
+                rescan_lane(R, g, text, s_q[k], s_e[k], ev, lane_cnt, lane_st, lane_np);
             __syncthreads();
             for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) s_prev[k] = s_q[k];
             if (threadIdx.x == 0) s_np = n;
@@ -1745,7 +1777,9 @@ constexpr int PAIRS_BLOCK = 256;
 
 // Two passes: k_pairs_flat<false> counts each lane's pairs (and records the AGENT rows' keyword
 // groups), an exclusive scan of the counts gives every lane its block of the queue (lane order, no
-// atomics), the write pass fills the blocks.
+// atomics), the write pass fills the blocks.  With one SCAN group and a pair queue to write, the scan
+// kernels have already counted the pairs (lane_pairs) and the count pass is not launched: the write
+// pass records the keyword groups (launch_front: scan_count).
 //
 // MULTI (a rule set split over several SCAN groups, config 5): every group's k_scan pass wrote its
 // own per-lane event list (descending position, arena g at ev + g * ev_stride), counted per group by
@@ -2085,7 +2119,10 @@ __global__ __launch_bounds__(MERGE_WAVES * 64) void k_pairs_merge(const Geo g, c
 // stores land in 64 different lines).  Pair numbering per lane is back to front (ascending by start,
 // as the per-lane form): a segmented scan of the events' pair counts plus each lane's running total.
 // Keyword groups of AGENT rows are merged with atomic min (init: k_chunk_index).
-template <bool WRITE>
+// KWG: the pass records the keyword groups -- the count pass always (and it alone when it runs); the
+// write pass when the lanes' pair counts came from the scan kernels and no count pass ran
+// (launch_front: scan_count), from the row it finds for every event anyway.
+template <bool WRITE, bool KWG = !WRITE>
 __global__ __launch_bounds__(PAIRS_BLOCK) void k_pairs_flat(const RulesDev R, const Geo g,
                                                     const Event* __restrict__ ev, const uint32_t* __restrict__ lane_cnt,
                                                     const uint8_t* __restrict__ role, int32_t* __restrict__ kw,
@@ -2099,6 +2136,9 @@ __global__ __launch_bounds__(PAIRS_BLOCK) void k_pairs_flat(const RulesDev R, co
                                                     uint32_t* __restrict__ lane_evn) {
     __shared__ uint32_t s_off[PAIRS_BLOCK / 64][PAIRS_UCAP + 1];
     __shared__ uint8_t s_role[PAIRS_BLOCK / 64][PAIRS_UCAP];
+    // (the write pass keeps "is an AGENT row" as one bit per row: the byte form's 4 KiB would cost it
+    // a workgroup per CU, 6 instead of 7 waves/SIMD)
+    __shared__ uint64_t s_agent[PAIRS_BLOCK / 64][PAIRS_UCAP / 64];
     __shared__ uint32_t s_aoff[257];
     __shared__ uint16_t s_aids[2048];
     if (*err & ERR_ARGS) return;
@@ -2123,12 +2163,32 @@ __global__ __launch_bounds__(PAIRS_BLOCK) void k_pairs_flat(const RulesDev R, co
     uint8_t* sr = s_role[wv];
     if (staged && cw0 < n_chunks) {
         for (uint32_t k = lane; k <= U1 - U0; k += 64) so[k] = (uint32_t)((int64_t)offs[U0 + k] - base);
-        if (!WRITE)
+        if (KWG && !WRITE)
             for (uint32_t k = lane; k < U1 - U0; k += 64) sr[k] = role[U0 + k];
+        if (KWG && WRITE) {
+            // (every load first, then the ballots: a ballot per load made the wavefront wait out one
+            // memory latency per 64 rows before its first event)
+            bool ag[PAIRS_UCAP / 64];
+#pragma unroll
+            for (uint32_t i = 0; i < (uint32_t)PAIRS_UCAP / 64; ++i) {
+                const uint32_t k = 64 * i + lane;
+                ag[i] = k < U1 - U0 && role[U0 + k] == PII_ROLE_AGENT;
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < (uint32_t)PAIRS_UCAP / 64; ++i) {
+                const uint64_t m = __ballot(ag[i]);
+                if (lane == 0) s_agent[wv][i] = m;
+            }
+        }
     }
     __syncthreads();
     if (cw0 >= n_chunks) return;
     auto uoff = [&](uint32_t u) { return staged ? so[u - U0] : (uint32_t)((int64_t)offs[u] - base); };
+    auto is_agent = [&](uint32_t u) {
+        if (!staged) return role[u] == PII_ROLE_AGENT;
+        if (WRITE) return (s_agent[wv][(u - U0) >> 6] >> ((u - U0) & 63u) & 1u) != 0;
+        return sr[u - U0] == PII_ROLE_AGENT;
+    };
     const bool valid = c < n_chunks;
     // count pass over several SCAN groups (config 5): blockIdx.y = group, its own event arena and
     // per-transition pair counts; only group 0 carries the keyword automaton.  The lanes' pair counts
@@ -2202,9 +2262,15 @@ __global__ __launch_bounds__(PAIRS_BLOCK) void k_pairs_flat(const RulesDev R, co
         (void)o_ex;
         uint32_t n = 0, acc = 0, u = 0, kg = (uint32_t)KW_NONE;
         if (act) {
-            n = npair[E.sd];
-            if (WRITE) acc = R.d_accid[E.sd];
-            else if (q == 0) kg = R.k_grp[E.sk];
+            if (WRITE && KWG) {         // (one gather for both: the keyword group's makes a third otherwise)
+                const uint32_t na = R.d_na[E.sd];
+                n = na & 0xffffu;
+                acc = na >> 16;
+            } else {
+                n = npair[E.sd];
+                if (WRITE) acc = R.d_accid[E.sd];
+            }
+            if (KWG && q == 0) kg = R.k_grp[E.sk];
             // the event's row (last u with start <= pos): the count pass needs it only for a keyword
             if (WRITE || kg != (uint32_t)KW_NONE) {
                 uint32_t lo = o_u0, hi = o_u1 - 1;
@@ -2234,8 +2300,10 @@ __global__ __launch_bounds__(PAIRS_BLOCK) void k_pairs_flat(const RulesDev R, co
                     Lc.uend = uoff(u + 1);
                     evloc[E0 + f] = Lc;
                 }
-            } else if (q == 0) {
-                if (kg != (uint32_t)KW_NONE && (staged ? sr[u - U0] : role[u]) == PII_ROLE_AGENT)
+            }
+            // (a keyword event with no D pairs still counts: not under the `if (n)` above)
+            if (KWG && q == 0) {
+                if (kg != (uint32_t)KW_NONE && is_agent(u))
                     atomicMin(reinterpret_cast<unsigned int*>(kw + u), kg);
             }
         }
@@ -5162,6 +5230,7 @@ struct pii_engine {
     uint32_t* lane_split = nullptr;    // k_scan2: per slot split point | A's arena capacity (k_lane_bits2)
     uint32_t* lane_spl = nullptr;      // the same per lane (k_lane_count)
     bool scan2 = false;                // two chains per lane in the SCAN (PII_SCAN2=1: k_scan2; slower)
+    bool scan_count = true;            // the scan kernels count each lane's pairs (PII_SCAN_COUNT=0: the count pass does)
     uint32_t halo_items = HALO_ITEMS;  // k_win_halo's item list per workgroup (PII_HALO_ITEMS: tests)
     bool scan_ilv = true;              // k_scan grids of <= n_cu workgroups deal wavefronts round-robin (PII_SCAN_ILV)
     uint32_t win_long = 0;             // incremental re-scan: rows longer than this many lanes are cut (PII_WIN_LONG; 0: never)
@@ -5572,6 +5641,13 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
             // last workgroups of its longest-first lanes -- overlaps the next passes.
             const uint32_t ns_scan = e->n_sg > 1 ? 1 + e->n_aux : 1;
             const bool two = ns_scan > 1;
+            // One SCAN group whose pair queue is written: the scan kernels (and a re-scan of k_scan_fix)
+            // leave each lane's pair count next to its event count, and the count pass is not launched
+            // -- the write pass records the keyword groups.  Several groups add their counts up in the
+            // count pass, and a call without a pair queue has no other producer of the keyword groups:
+            // both keep it.
+            const bool scan_count = e->scan_count && e->n_sg == 1 && pair_first;
+            uint32_t* const scan_np = scan_count ? e->lane_np : nullptr;
             for (uint32_t q = 0; q < e->n_sg; ++q) {
                 const RulesDev& Rq = e->sg[q];
                 Event* evq = e->ev + (uint64_t)q * e->cap_ev;
@@ -5605,12 +5681,12 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                     (q == 0 ? k_scan2<true> : one_wg ? k_scan2<false, SCAN_BLOCK_WIDE> : k_scan2<false>)<<<
                         (n_chunks + nt2 - 1) / nt2, nt2, e->sg_lds[q], sq>>>(
                         Rq, g, text, reinterpret_cast<const uint32_t*>(e->bnd), e->lane_split, e->lane_perm, evq,
-                        cq, stq, e->d_err);
+                        cq, stq, e->d_err, scan_np);
                 } else {
                     const uint32_t nb = (n_chunks + nt - 1) / nt;
                     (q == 0 ? k_scan<true> : one_wg ? k_scan<false, SCAN_BLOCK_WIDE> : k_scan<false>)<<<
                         nb, nt, e->sg_lds[q], sq>>>(Rq, g, text, e->bnd, e->lane_perm, evq, cq, stq, e->d_err,
-                                                    e->scan_ilv && nb <= e->n_cu ? nb : 0u);
+                                                    e->scan_ilv && nb <= e->n_cu ? nb : 0u, scan_np);
                 }
             }
             for (uint32_t i = 0; i + 1 < ns_scan; ++i) {
@@ -5621,16 +5697,17 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
             if (e->long_min != NO_CUTS)
                 k_scan_fix<<<dim3(row_grid(e, total_bytes), e->n_sg), 256, e->max_sg_lds + FIX_LDS, st>>>(
                     e->d_sg, e->d_sg_lds, g, text, e->long_rows, e->long_count, e->ev, e->cap_ev, e->lane_cnt,
-                    e->lane_st, e->cap_lanes, e->d_err);
+                    e->lane_st, e->cap_lanes, e->d_err, scan_np);
             const uint32_t nbp = (n_chunks + PAIRS_BLOCK - 1) / PAIRS_BLOCK;
             const bool multi = e->n_sg > 1;
             const uint32_t ns = e->n_sg, cs = (uint32_t)e->cap_lanes;
             const uint64_t es = e->cap_ev;
             if (multi) HIPCHK(hipMemsetAsync(e->lane_np, 0, (size_t)n_chunks * sizeof(uint32_t), st));
-            k_pairs_flat<false><<<dim3(nbp, ns), PAIRS_BLOCK, 0, st>>>(R, g, e->ev, e->lane_cnt, role, e->kw, e->evloc,
-                                                                       e->pair_cap, e->ev_cap, e->lane_pair,
-                                                                       e->lane_ev, e->lane_np, e->d_err, e->pres, e->acct,
-                                                                       ns, es, cs, e->lane_evn);
+            if (!scan_count)
+                k_pairs_flat<false><<<dim3(nbp, ns), PAIRS_BLOCK, 0, st>>>(R, g, e->ev, e->lane_cnt, role, e->kw, e->evloc,
+                                                                           e->pair_cap, e->ev_cap, e->lane_pair,
+                                                                           e->lane_ev, e->lane_np, e->d_err, e->pres, e->acct,
+                                                                           ns, es, cs, e->lane_evn);
             int rc;
             if ((rc = exclusive_scan(e, e->lane_np, n_chunks, e->lane_pair, st, multi ? e->lane_evn : e->lane_cnt,
                                      n_chunks, e->lane_ev)))
@@ -5644,10 +5721,9 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                     g, e->ev, e->lane_cnt, e->evloc, e->pres, R.d_acc_off, R.d_acc_ids, e->pair_cap, e->ev_cap,
                     e->lane_pair, e->lane_ev, e->lane_np, e->d_err, ns, es, cs, e->acct, e->merge_cap);
             } else {
-                k_pairs_flat<true><<<nbp, PAIRS_BLOCK, 0, st>>>(R, g, e->ev, e->lane_cnt, role, e->kw, e->evloc,
-                                                                e->pair_cap, e->ev_cap, e->lane_pair,
-                                                                e->lane_ev, e->lane_np, e->d_err, e->pres, e->acct,
-                                                                1, 0, 0, nullptr);
+                (scan_count ? k_pairs_flat<true, true> : k_pairs_flat<true>)<<<nbp, PAIRS_BLOCK, 0, st>>>(
+                    R, g, e->ev, e->lane_cnt, role, e->kw, e->evloc, e->pair_cap, e->ev_cap, e->lane_pair, e->lane_ev,
+                    e->lane_np, e->d_err, e->pres, e->acct, 1, 0, 0, nullptr);
             }
         }
         HIPCHK(hipGetLastError());
@@ -6369,7 +6445,10 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
             for (size_t i = 0; i < h.dacc.size(); ++i) h.npair[i] = (uint16_t)(off[h.dacc[i] + 1] - off[h.dacc[i]]);
         }
     }
+    std::vector<uint32_t> d_na(dacc.size());
+    for (size_t i = 0; i < dacc.size(); ++i) d_na[i] = d_npair[i] | (uint32_t)dacc[i] << 16;
     size_t i_dnp = add(d_npair.data(), d_npair.size() * 2), i_kgrp = add(k_grp.data(), k_grp.size() * 2);
+    size_t i_dna = add(d_na.data(), d_na.size() * 4);
     size_t i_dt = addsec("det.type"), i_dv = addsec("det.validator"), i_dl = addsec("det.lik"),
            i_dx = addsec("det.exidx"), i_fd = addsec("det.first_desc"), i_hr = addsec("hot.rule"),
            i_hd = addsec("hot.dfa_desc"), i_ve = addsec("var.enabled"), i_vm = addsec("var.minlik"),
@@ -6399,6 +6478,7 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
     R.k_accid = (const uint16_t*)at(i_kacc);
     R.k_acc_min = (const uint16_t*)at(i_kmin);
     R.d_npair = (const uint16_t*)at(i_dnp);
+    R.d_na = (const uint32_t*)at(i_dna);
     R.k_grp = (const uint16_t*)at(i_kgrp);
     R.det_type = (const uint16_t*)at(i_dt);
     R.det_val = (const uint8_t*)at(i_dv);
@@ -6666,6 +6746,7 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
             return fail("hipMalloc failed");
     }
     if (const char* v = std::getenv("PII_SCAN2")) e->scan2 = std::atoi(v) != 0;
+    if (const char* v = std::getenv("PII_SCAN_COUNT")) e->scan_count = std::atoi(v) != 0;
     if (const char* v = std::getenv("PII_SCAN_ILV")) e->scan_ilv = std::atoi(v) != 0;
     if (const char* v = std::getenv("PII_WIN_LONG")) e->win_long = (uint32_t)std::max(0, std::min(64, std::atoi(v)));
     if (const char* v = std::getenv("PII_HALO_ITEMS")) e->halo_items = (uint32_t)std::max(0, std::min(HALO_ITEMS, std::atoi(v)));
