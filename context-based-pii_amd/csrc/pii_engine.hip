@@ -65,10 +65,12 @@ constexpr int KW_NONE = 0x7fff;
 constexpr int PAIRS_UCAP = 1024;   // utterances a wavefront stages in LDS (k_pairs_flat)
 
 enum : uint32_t { ERR_CAPACITY = 1, ERR_ORDER = 2, ERR_SLOT = 4, ERR_QUEUE = 8, ERR_RING = 16, ERR_STITCH = 32,
-                  ERR_ARGS = 64, ERR_EXT = 128 };
+                  ERR_ARGS = 64, ERR_EXT = 128, ERR_LONG = 256 };
 // a call whose declared batch size was wrong (ERR_ARGS) or whose queues overflowed (ERR_QUEUE, re-run by
 // pii_sync) stops every later stage
-constexpr uint32_t ERR_ABORT = ERR_QUEUE | ERR_ARGS;
+// ERR_LONG: a cut row in a call that did not launch the long-row kernels (the long-row gate, launch_front);
+// re-run by pii_sync with them, like ERR_QUEUE.
+constexpr uint32_t ERR_ABORT = ERR_QUEUE | ERR_ARGS | ERR_LONG;
 
 struct Event {
     uint32_t pos;   // candidate start, relative to the batch base
@@ -237,7 +239,7 @@ __global__ __launch_bounds__(256) void k_chunk_index(const uint64_t* __restrict_
                                                      int32_t* __restrict__ kw, uint32_t* __restrict__ wc_n,
                                                      uint32_t* __restrict__ long_rows, uint32_t* __restrict__ long_count,
                                                      uint32_t long_cap, uint64_t decl_base, uint64_t decl_bytes,
-                                                     uint32_t* __restrict__ err) {
+                                                     uint32_t* __restrict__ err, bool long_kernels) {
     const uint32_t u0 = (blockIdx.x * blockDim.x + threadIdx.x) * CI_ROWS;
     if (u0 > n_utt) return;
     const uint64_t base = offs[0];
@@ -283,12 +285,15 @@ __global__ __launch_bounds__(256) void k_chunk_index(const uint64_t* __restrict_
             wbase = __shfl(wbase, lead);
             if (cut) {
                 const uint32_t at = wbase + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-                if (at < long_cap) {
-                    long_rows[at] = u;
-                } else {
-                    atomicOr(err, (uint32_t)ERR_STITCH);      // (sized by ensure_scratch: internal)
+                if (at < long_cap) long_rows[at] = u;
+                else atomicOr(err, (uint32_t)ERR_STITCH);     // (sized by ensure_scratch: internal)
+                // the long-row kernels were not launched (the gate is closed): the call is void and is
+                // run again with them.  The row's slices are filled here, serially, as for a row past
+                // the list: every later kernel takes its lane geometry from first_utt, and entries left
+                // from an earlier call would index offs out of range.
+                if (!long_kernels) atomicOr(err, (uint32_t)ERR_LONG);
+                if (!long_kernels || at >= long_cap)
                     fill_after(first_utt, u, o[k + 1] - base, o[k + 2] - base, n_utt, n_chunks, lane_shift, r0, 0, 1);
-                }
             }
         }
     }
@@ -3256,12 +3261,35 @@ __device__ uint64_t block_exscan(uint64_t (&v)[SCAN_ITEMS], uint64_t* sh) {
 // Up to two independent scans per launch (blockIdx.y picks one: the two per-lane scans of the front go
 // together); a thread owns SCAN_ITEMS consecutive entries, read / written with 16-byte accesses when
 // the arrays allow it.
+// what closes a scan-and-redact call once its row and span scans are done (k_finalize); totals == null
+// for every scan that does not end one
+struct ScanFin {
+    uint64_t* totals;
+    uint32_t* err;
+    const unsigned long long* pair_count;
+    const uint64_t* ev_count;
+    const uint32_t* long_count;
+    uint64_t out_cap, span_cap;
+};
 struct ScanArgs {
     const uint32_t* in[2];
     uint64_t* out[2];
     uint32_t n[2];
     uint32_t bstride;            // block sums of scan 1 at bsum + bstride
+    ScanFin fin;                 // scan 0 = row output lengths, scan 1 = spans per lane
 };
+
+// capacity test and the call's totals, from the two scans' totals (one thread)
+__device__ __forceinline__ void finalize_call(const ScanFin& f, uint64_t ob, uint64_t ns) {
+    if (ob > f.out_cap || ns > f.span_cap) atomicOr(f.err, (uint32_t)ERR_CAPACITY);
+    f.totals[0] = ob;
+    f.totals[1] = ns;
+    f.totals[2] = *f.err;
+    f.totals[3] = *f.pair_count;
+    f.totals[4] = f.ev_count ? *f.ev_count : 0;
+    f.totals[5] = 0;
+    f.totals[6] = f.long_count ? *f.long_count : 0;
+}
 
 __device__ __forceinline__ void scan_load(const uint32_t* __restrict__ in, uint32_t n, uint64_t i0,
                                           uint32_t (&v)[SCAN_ITEMS]) {
@@ -3323,6 +3351,11 @@ __global__ __launch_bounds__(256) void k_scan_apply(const ScanArgs a, const uint
     const int y = blockIdx.y;
     const uint32_t n = a.n[y];
     const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE;
+    // the call's totals and capacity test (k_finalize's work: both scans' totals are behind their sums
+    // since k_scan_blocks), once, ahead of the kernels that test the error word
+    if (a.fin.totals && blockIdx.x == 0 && y == 0 && threadIdx.x == 0)
+        finalize_call(a.fin, bsum[(a.n[0] + SCAN_TILE - 1) / SCAN_TILE],
+                      bsum[a.bstride + (a.n[1] + SCAN_TILE - 1) / SCAN_TILE]);
     if (base >= n) {
         if (base == 0 && threadIdx.x == 0) a.out[y][0] = 0;
         return;
@@ -3486,15 +3519,11 @@ __global__ __launch_bounds__(LB_BLOCK) void k_scan_lb(const LbArgs a, unsigned l
 __global__ void k_finalize(const uint64_t* __restrict__ out_offs, const uint64_t* __restrict__ span_offs,
                            uint32_t n_utt, uint32_t n_span_rows, uint64_t out_cap, uint64_t span_cap, uint32_t* __restrict__ err,
                            uint64_t* __restrict__ totals, const unsigned long long* __restrict__ pair_count,
-                           const uint64_t* __restrict__ ev_count, const uint64_t* __restrict__ wf_count) {
-    const uint64_t ob = out_offs[n_utt], ns = span_offs[n_span_rows];
-    if (ob > out_cap || ns > span_cap) atomicOr(err, (uint32_t)ERR_CAPACITY);
-    totals[0] = ob;
-    totals[1] = ns;
-    totals[2] = *err;
-    totals[3] = *pair_count;
-    totals[4] = ev_count ? *ev_count : 0;
-    totals[5] = wf_count ? *wf_count : 0;
+                           const uint64_t* __restrict__ ev_count, const uint64_t* __restrict__ wf_count,
+                           const uint32_t* __restrict__ long_count) {
+    finalize_call(ScanFin{totals, err, pair_count, ev_count, long_count, out_cap, span_cap}, out_offs[n_utt],
+                  span_offs[n_span_rows]);
+    if (wf_count) totals[5] = *wf_count;
 }
 
 // ---------------------------------------------------------------------------------- k_redact
@@ -5010,7 +5039,7 @@ __global__ void k_err_save(const uint32_t* __restrict__ cnt, uint32_t* __restric
 __global__ void k_ctx_totals(const uint32_t* __restrict__ err, uint64_t* __restrict__ totals) {
     totals[0] = totals[1] = 0;
     totals[2] = *err;
-    totals[3] = totals[4] = totals[5] = 0;
+    totals[3] = totals[4] = totals[5] = totals[6] = 0;
 }
 
 // a call's first kernel: its counter block (err, long_count, ncommit, pair_count) from zero or from a
@@ -5231,6 +5260,16 @@ struct pii_engine {
     uint32_t* lane_spl = nullptr;      // the same per lane (k_lane_count)
     bool scan2 = false;                // two chains per lane in the SCAN (PII_SCAN2=1: k_scan2; slower)
     bool scan_count = true;            // the scan kernels count each lane's pairs (PII_SCAN_COUNT=0: the count pass does)
+    // The long-row gate (launch_front): whether a workload has rows that get cut is a property of the
+    // workload, not of one batch, so a scan-and-redact call launches the long-row kernels only while cut
+    // rows are expected.  A cut row in a call without them sets ERR_LONG and pii_sync runs the call again.
+    bool long_gate = true;             // PII_LONG_GATE=0: every call launches the long-row kernels
+    bool long_expect = false;          // the next call launches them
+    uint32_t long_idle = 0;            // completed calls in a row without a cut row
+    bool last_gated = false;           // the last call was one the gate applies to
+    bool gate_pending = false;         // ... and pii_sync has not yet taken its cut-row count into the state
+    bool last_long_launched = true;    // ... and launched the long-row kernels
+    uint32_t last_reruns = 0;          // re-runs the last pii_sync did
     uint32_t halo_items = HALO_ITEMS;  // k_win_halo's item list per workgroup (PII_HALO_ITEMS: tests)
     bool scan_ilv = true;              // k_scan grids of <= n_cu workgroups deal wavefronts round-robin (PII_SCAN_ILV)
     uint32_t win_long = 0;             // incremental re-scan: rows longer than this many lanes are cut (PII_WIN_LONG; 0: never)
@@ -5508,10 +5547,13 @@ int ensure_redact(pii_engine* e, uint64_t span_cap, uint64_t out_cap) {
 // Small scans (a re-scan step: ~100k rows) take the single-pass look-back kernel, one launch instead
 // of three; big ones (10M rows) the reduce / scan-of-sums / apply triple, whose tiles never wait on
 // each other (the look-back's cross-XCD hand-offs chain up over thousands of tiles: 0.4 ms vs 0.06).
+// `fin`: the pair of scans ends a scan-and-redact call; on the big path k_scan_apply does k_finalize's
+// work and *fin_done is set, else the caller launches k_finalize.
 constexpr uint32_t LB_MAX_TILES = 64;
 
 int exclusive_scan(pii_engine* e, const uint32_t* in, uint32_t n, uint64_t* out, hipStream_t st,
-                   const uint32_t* in2 = nullptr, uint32_t n2 = 0, uint64_t* out2 = nullptr) {
+                   const uint32_t* in2 = nullptr, uint32_t n2 = 0, uint64_t* out2 = nullptr,
+                   const ScanFin* fin = nullptr, bool* fin_done = nullptr) {
     const uint32_t nb = (n + LB_TILE - 1) / LB_TILE, nb2 = in2 ? (n2 + LB_TILE - 1) / LB_TILE : 0;
     if (in2 == nullptr && nb == 0) {
         HIPCHK(hipMemsetAsync(out, 0, sizeof(uint64_t), st));
@@ -5520,10 +5562,14 @@ int exclusive_scan(pii_engine* e, const uint32_t* in, uint32_t n, uint64_t* out,
     // (a scan of zero items still writes its total: the look-back form needs a tile for it)
     if (nb > LB_MAX_TILES || nb2 > LB_MAX_TILES || (in2 && (nb == 0 || nb2 == 0))) {
         // reduce / scan-of-sums / apply; a second scan rides along in blockIdx.y
-        ScanArgs a{{in, in2 ? in2 : in}, {out, out2 ? out2 : out}, {n, in2 ? n2 : 0u}, 0};
+        ScanArgs a{{in, in2 ? in2 : in}, {out, out2 ? out2 : out}, {n, in2 ? n2 : 0u}, 0, ScanFin{}};
         const uint32_t nt = std::max<uint32_t>(1, (std::max(n, a.n[1]) + SCAN_TILE - 1) / SCAN_TILE);
         a.bstride = nt + 2;
         const uint32_t ny = in2 ? 2 : 1;
+        if (fin && in2) {
+            a.fin = *fin;
+            *fin_done = true;
+        }
         k_scan_reduce<<<dim3(nt, ny), 256, 0, st>>>(a, e->bsum);
         k_scan_blocks<<<ny, 256, 0, st>>>(a, e->bsum);
         k_scan_apply<<<dim3(nt, ny), 256, 0, st>>>(a, e->bsum);
@@ -5601,12 +5647,17 @@ size_t hist_bytes(const pii_engine* e) { return 64 + (size_t)std::max(e->R.T, 25
 
 // The stages every call shares: lane index, reverse DFA scan (+ the stitching of cut rows), (start,
 // pattern) pair queue, context (segmented scan), leftmost-first confirmation.  Records tev[0..2].
+// long_kernels = false (the long-row gate is closed): k_fill_long, k_halo and k_scan_fix are not launched,
+// and k_chunk_index fails the call with ERR_LONG if it meets a cut row after all.
+constexpr uint32_t LONG_IDLE_CALLS = 8;      // calls without a cut row after which the gate closes again
 int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint32_t n_utt, uint32_t n_chunks,
                  uint64_t base, uint64_t total_bytes, const uint32_t* slot, const uint8_t* role, const int64_t* ts,
                  int16_t* ctx, int16_t* win_ctx, const unsigned long long* pcount, hipStream_t st,
-                 const uint32_t* err_init = nullptr, bool ctx_kernels = true, bool pair_first = true) {
+                 bool long_kernels, const uint32_t* err_init = nullptr, bool ctx_kernels = true,
+                 bool pair_first = true) {
     const RulesDev& R = e->R;
     e->epoch += 1;
+    const bool long_k = long_kernels && e->long_min != NO_CUTS;
     const Geo g = make_geo(e, offs, n_utt, n_chunks, base);
     // counter block (a second pass over the call starts from the first pass's), lane buckets, and the
     // histogram if pii_histogram_reset was called since the last call
@@ -5619,8 +5670,8 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                                                                 e->long_min, R.kw_always_min, e->first_utt,
                                                                 e->out_len, e->kw, win_ctx ? e->wc_n : nullptr,
                                                                 e->long_rows, e->long_count, (uint32_t)e->cap_long, base,
-                                                                total_bytes, e->d_err);
-        if (e->long_min != NO_CUTS)
+                                                                total_bytes, e->d_err, long_kernels);
+        if (long_k)
             k_fill_long<<<row_grid(e, total_bytes), 256, 0, st>>>(offs, n_utt, n_chunks, e->lane_shift, e->r0, e->long_rows,
                                                                    e->long_count, (uint32_t)e->cap_long, e->first_utt);
         if (n_chunks > 0) {
@@ -5659,7 +5710,7 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                                                                          e->lane_split);
                 else if (q == 0)
                     k_lane_bits<<<(n_chunks + 255) / 256, 256, 0, st>>>(g, e->lane_pos, e->bnd);
-                if (!SCAN_INLINE_HALO && e->long_min != NO_CUTS)
+                if (!SCAN_INLINE_HALO && long_k)
                     k_halo<<<row_grid(e, total_bytes), HALO_BLOCK, e->sg_lds[q], st>>>(Rq, g, text, e->long_rows,
                                                                                   e->long_count, stq, e->d_err);
                 if (q == 0) {
@@ -5694,7 +5745,7 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                 HIPCHK(hipStreamWaitEvent(st, e->ev_join[i], 0));
             }
             if (e->timing >= 1) HIPCHK(hipEventRecord(e->kev[1], st));
-            if (e->long_min != NO_CUTS)
+            if (long_k)
                 k_scan_fix<<<dim3(row_grid(e, total_bytes), e->n_sg), 256, e->max_sg_lds + FIX_LDS, st>>>(
                     e->d_sg, e->d_sg_lds, g, text, e->long_rows, e->long_count, e->ev, e->cap_ev, e->lane_cnt,
                     e->lane_st, e->cap_lanes, e->d_err, scan_np);
@@ -5799,6 +5850,10 @@ int run_pipeline(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                                    span_cap, ctx_info, st, ext, ext_n, ext_stride};
         e->last_kind = 0;
     }
+    // the long-row gate: plain scan-and-redact calls only (the window paths always launch)
+    e->last_gated = e->gate_pending = !wf && e->long_min != NO_CUTS;
+    const bool long_k = !e->last_gated || !e->long_gate || e->long_expect;
+    e->last_long_launched = long_k;
     const RulesDev& R = e->R;
     int16_t* ctx = wf ? const_cast<int16_t*>(wf->ctx_given) : ctx_info ? ctx_info : e->ctx;
     e->kev_valid = n_utt > 0 && total_bytes > 0;
@@ -5807,7 +5862,7 @@ int run_pipeline(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
     const unsigned long long* pcount =
         n_chunks > 0 ? reinterpret_cast<const unsigned long long*>(e->lane_pair + n_chunks) : e->pair_count;
     if ((rc = launch_front(e, text, offs, n_utt, n_chunks, base, total_bytes, slot, role, ts, ctx, nullptr, pcount,
-                           st, wf ? wf->err_init : nullptr, wf == nullptr)))
+                           st, long_k, wf ? wf->err_init : nullptr, wf == nullptr)))
         return rc;
     if (n_utt > 0 && n_chunks > 0) {
         if (e->img_eval_rg.d) {
@@ -5842,25 +5897,34 @@ int run_pipeline(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                        : (has_ext ? (gi ? k_sel_fix<true, true> : k_sel_fix<false, true>)
                                   : (gi ? k_sel_fix<true, false> : k_sel_fix<false, false>));
         ksel<<<(n_chunks + 255) / 256, 256, isel.lds(), st>>>(Rsel, isel.d, isel.li, g, io, e->d_err);
-        const uint32_t rg = row_grid(e, total_bytes);
-        k_sel_dirty<<<rg, ROW_BLOCK, 0, st>>>(g, e->long_rows, e->long_count, e->lane_reach, e->dirty, e->d_err);
-        kfix<<<rg, 256, isel.lds(), st>>>(Rsel, isel.d, isel.li, g, io, e->long_rows, e->long_count,
-                                                 e->dirty, e->d_err);
-        k_rowlen<<<rg, ROW_BLOCK, 0, st>>>(g, e->long_rows, e->long_count, e->lane_rd, e->lane_rowbase, e->out_len,
-                                          e->d_err);
+        if (long_k) {
+            const uint32_t rg = row_grid(e, total_bytes);
+            k_sel_dirty<<<rg, ROW_BLOCK, 0, st>>>(g, e->long_rows, e->long_count, e->lane_reach, e->dirty, e->d_err);
+            kfix<<<rg, 256, isel.lds(), st>>>(Rsel, isel.d, isel.li, g, io, e->long_rows, e->long_count, e->dirty,
+                                              e->d_err);
+            k_rowlen<<<rg, ROW_BLOCK, 0, st>>>(g, e->long_rows, e->long_count, e->lane_rd, e->lane_rowbase, e->out_len,
+                                               e->d_err);
+        }
         HIPCHK(hipGetLastError());
     }
     if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[3], st));
     // row output offsets and per-lane span offsets: one dual scan (a big batch: 3 launches instead of
     // 6; a small one: one single-pass look-back launch instead of 2)
+    // (a big batch: k_scan_apply closes the call, as k_finalize does for a small one or a window's)
+    const uint64_t* ev_count = n_chunks > 0 ? e->lane_ev + n_chunks : nullptr;
+    bool fin_done = false;
     if (n_chunks > 0) {
-        if ((rc = exclusive_scan(e, e->out_len, n_utt, out_offs, st, e->lane_nf, n_chunks, e->lane_sp))) return rc;
+        const ScanFin fin{e->d_totals, e->d_err, pcount, ev_count, e->long_count, out_cap, span_cap};
+        if ((rc = exclusive_scan(e, e->out_len, n_utt, out_offs, st, e->lane_nf, n_chunks, e->lane_sp, wf ? nullptr : &fin,
+                                 &fin_done)))
+            return rc;
     } else {
         if ((rc = exclusive_scan(e, e->out_len, n_utt, out_offs, st))) return rc;
         if ((rc = exclusive_scan(e, e->lane_nf, n_chunks, e->lane_sp, st))) return rc;
     }
-    k_finalize<<<1, 1, 0, st>>>(out_offs, e->lane_sp, n_utt, n_chunks, out_cap, span_cap, e->d_err, e->d_totals,
-                                pcount, n_chunks > 0 ? e->lane_ev + n_chunks : nullptr, nullptr);
+    if (!fin_done)
+        k_finalize<<<1, 1, 0, st>>>(out_offs, e->lane_sp, n_utt, n_chunks, out_cap, span_cap, e->d_err, e->d_totals,
+                                    pcount, ev_count, nullptr, e->long_count);
     HIPCHK(hipGetLastError());
     if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[4], st));
     if (n_utt > 0) {
@@ -5991,11 +6055,12 @@ int run_window_full(pii_engine* e, const uint8_t* text, const uint64_t* offs, ui
     e->last = pii_engine::Call{text, offs, n_utt, base, total_bytes, slot, role, ts, out, out_cap, out_offs, spans,
                                span_cap, win_ctx, st, nullptr, nullptr, 0};
     e->last_kind = 1;
+    e->last_gated = false;
     int16_t* wctx = win_ctx ? win_ctx : e->wctx;
     const unsigned long long* pcount =
         n_chunks > 0 ? reinterpret_cast<const unsigned long long*>(e->lane_pair + n_chunks) : e->pair_count;
     if ((rc = launch_front(e, text, offs, n_utt, n_chunks, base, total_bytes, slot, role, ts, e->ctx, wctx, pcount, st,
-                           nullptr, true, false)))
+                           true, nullptr, true, false)))
         return rc;
     const WinRing W{e->wr_desc, e->wr_cnt, e->wr_head, e->wr_arena, e->win_n, e->win_slot_bytes, e->n_slots, 0};
     if (n_utt) HIPCHK(hipMemsetAsync(e->wc_n, 0, (size_t)n_utt * 4, st));      // text-only ring entries
@@ -6067,7 +6132,7 @@ int run_window(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint32_
     const unsigned long long* pcount =
         n_chunks > 0 ? reinterpret_cast<const unsigned long long*>(e->lane_pair + n_chunks) : e->pair_count;
     if ((rc = launch_front(e, text, offs, n_utt, n_chunks, base, total_bytes, slot, role, ts, e->ctx, wctx, pcount,
-                           st)))
+                           st, true)))
         return rc;
     if (n_utt > 0 && n_chunks > 0) {
         (e->img_eval.global ? k_win_eval<true> : k_win_eval<false>)<<<e->n_seg, PAIR_BLOCK, e->img_eval.lds(), st>>>(
@@ -6105,7 +6170,8 @@ int run_window(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint32_
     }
     if (n_utt > 0) k_win_alloc<<<nb, 256, 0, st>>>(W, B, e->wnew, e->d_err);
     k_finalize<<<1, 1, 0, st>>>(out_offs, e->wspan_offs, n_utt, n_utt, out_cap, span_cap, e->d_err, e->d_totals,
-                                pcount, n_chunks > 0 ? e->lane_ev + n_chunks : nullptr, n_utt > 0 ? e->wfbase + n_utt : nullptr);
+                                pcount, n_chunks > 0 ? e->lane_ev + n_chunks : nullptr, n_utt > 0 ? e->wfbase + n_utt : nullptr,
+                                nullptr);
     HIPCHK(hipGetLastError());
     if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[4], st));
     if (n_utt > 0) {
@@ -6143,11 +6209,12 @@ int run_context(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint32
     e->last = pii_engine::Call{text, offs, n_utt, 0, total_bytes, slot, role, ts, nullptr, 0, nullptr, nullptr,
                                0, ctx_info, st, nullptr, nullptr, 0};
     e->last_kind = 2;
+    e->last_gated = false;
     e->kev_valid = false;
     const unsigned long long* pcount =
         n_chunks > 0 ? reinterpret_cast<const unsigned long long*>(e->lane_pair + n_chunks) : e->pair_count;
     if ((rc = launch_front(e, text, offs, n_utt, n_chunks, 0, total_bytes, slot, role, ts, ctx_info, nullptr, pcount,
-                           st, nullptr, true, false)))
+                           st, true, nullptr, true, false)))
         return rc;
     if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[3], st));
     k_ctx_totals<<<1, 1, 0, st>>>(e->d_err, e->d_totals);
@@ -6747,6 +6814,7 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
     }
     if (const char* v = std::getenv("PII_SCAN2")) e->scan2 = std::atoi(v) != 0;
     if (const char* v = std::getenv("PII_SCAN_COUNT")) e->scan_count = std::atoi(v) != 0;
+    if (const char* v = std::getenv("PII_LONG_GATE")) e->long_gate = std::atoi(v) != 0;
     if (const char* v = std::getenv("PII_SCAN_ILV")) e->scan_ilv = std::atoi(v) != 0;
     if (const char* v = std::getenv("PII_WIN_LONG")) e->win_long = (uint32_t)std::max(0, std::min(64, std::atoi(v)));
     if (const char* v = std::getenv("PII_HALO_ITEMS")) e->halo_items = (uint32_t)std::max(0, std::min(HALO_ITEMS, std::atoi(v)));
@@ -6920,24 +6988,45 @@ int pii_reserve(pii_engine* e, uint32_t max_utt, uint64_t max_bytes, uint64_t ma
 int pii_sync(pii_engine* e, uint64_t totals[3]) {
     if (!e) return PII_E_ARG;
     HIPCHK(hipEventSynchronize(e->tev[6]));
-    for (int attempt = 0; (e->h_totals[2] & ERR_QUEUE) && !(e->h_totals[2] & ERR_ARGS) && attempt < 4; ++attempt) {
+    e->last_reruns = 0;
+    for (int attempt = 0; (e->h_totals[2] & (ERR_QUEUE | ERR_LONG)) && !(e->h_totals[2] & ERR_ARGS) && attempt < 4;
+         ++attempt) {
         // a work queue overflowed (pair queue, event records, window findings): grow it to the exact
         // need and run the batch again (context and window history were not committed, so the re-run
-        // is idempotent)
-        const uint64_t need = e->h_totals[3] + 4096, need_ev = e->h_totals[4] + 4096, need_wf = e->h_totals[5] + 4096;
-        if (need_ev > e->ev_cap) {
-            if (int rc = grow(e, e->evloc, need_ev)) return rc;
-            e->ev_cap = need_ev;
+        // is idempotent).  A cut row in a call that did not launch the long-row kernels (ERR_LONG): the
+        // same, with them.
+        int rc;
+        ++e->last_reruns;
+        if (e->h_totals[2] & ERR_LONG) {
+            e->long_expect = true;
+            e->long_idle = 0;
         }
-        int rc = grow_pairs(e, std::max(need, e->pair_cap));
-        if (rc) return rc;
-        e->pair_cap = std::max(need, e->pair_cap);
-        if (e->last_kind == 1 && need_wf > e->wfd_cap) {
-            if ((rc = grow(e, e->wfd, need_wf))) return rc;
-            e->wfd_cap = need_wf;
+        if (e->h_totals[2] & ERR_QUEUE) {
+            const uint64_t need = e->h_totals[3] + 4096, need_ev = e->h_totals[4] + 4096, need_wf = e->h_totals[5] + 4096;
+            if (need_ev > e->ev_cap) {
+                if ((rc = grow(e, e->evloc, need_ev))) return rc;
+                e->ev_cap = need_ev;
+            }
+            if ((rc = grow_pairs(e, std::max(need, e->pair_cap)))) return rc;
+            e->pair_cap = std::max(need, e->pair_cap);
+            if (e->last_kind == 1 && need_wf > e->wfd_cap) {
+                if ((rc = grow(e, e->wfd, need_wf))) return rc;
+                e->wfd_cap = need_wf;
+            }
         }
         if ((rc = rerun_last(e))) return rc;
         HIPCHK(hipEventSynchronize(e->tev[6]));
+    }
+    // the long-row gate follows the workload: open from the first cut row on, closed again after
+    // LONG_IDLE_CALLS calls without one
+    if (e->last_gated && e->gate_pending && !(e->h_totals[2] & ERR_ARGS)) {
+        e->gate_pending = false;
+        if (e->h_totals[6]) {
+            e->long_expect = true;
+            e->long_idle = 0;
+        } else if (++e->long_idle >= LONG_IDLE_CALLS) {
+            e->long_expect = false;
+        }
     }
     float tot = 0;
     for (int i = 0; i < 5; ++i) {
@@ -7006,10 +7095,11 @@ int pii_last_queue_sizes(pii_engine* e, uint64_t* pairs, uint64_t* events) {
 
 int pii_last_stats(pii_engine* e, uint64_t* out, uint32_t n) {
     if (!e || (!out && n)) return PII_E_ARG;
-    const uint64_t all[6] = {e->h_totals[3], e->h_totals[4], e->last_lanes, 1ull << e->lane_shift, e->h_totals[5],
-                             e->h_totals[1]};
-    for (uint32_t i = 0; i < n && i < 6; ++i) out[i] = all[i];
-    return (int)std::min<uint32_t>(n, 6);
+    const uint64_t all[9] = {e->h_totals[3], e->h_totals[4], e->last_lanes, 1ull << e->lane_shift, e->h_totals[5],
+                             e->h_totals[1], e->last_gated ? e->h_totals[6] : 0, e->last_long_launched ? 1u : 0u,
+                             e->last_reruns};
+    for (uint32_t i = 0; i < n && i < 9; ++i) out[i] = all[i];
+    return (int)std::min<uint32_t>(n, 9);
 }
 
 int pii_last_timings_ex(pii_engine* e, float* ms, uint32_t n) {

@@ -384,13 +384,18 @@ class Engine:
         self.lib.pii_last_queue_sizes(self.h, ctypes.byref(a), ctypes.byref(b))
         return int(a.value), int(b.value)
 
-    def stats(self) -> dict:
-        """work sizes of the last call (pii_last_stats)"""
-        a = (ctypes.c_uint64 * 6)()
-        n = self.lib.pii_last_stats(self.h, a, 6)
+    def stats(self, gate: bool = False) -> dict:
+        """work sizes of the last call (pii_last_stats).  gate=True adds the long-row gate's record of it:
+        rows cut into several lanes, whether the long-row kernels were launched, and the re-runs its sync
+        did.  Those depend on the calls the engine saw before, not on the batch alone, so two engines
+        given the same batch agree on the default entries only."""
+        want = 9 if gate else 6
+        a = (ctypes.c_uint64 * 9)()
+        n = self.lib.pii_last_stats(self.h, a, want)
         if n < 0:
             raise self._err(n, "pii_last_stats")
-        keys = ["pairs", "events", "lanes", "lane_bytes", "window_findings_arena", "spans"]
+        keys = ["pairs", "events", "lanes", "lane_bytes", "window_findings_arena", "spans", "cut_rows",
+                "long_kernels_launched", "reruns"]
         return {k: int(a[i]) for i, k in enumerate(keys[:n])}
 
     # ------------------------------------------------------------------ context + histogram

@@ -170,7 +170,14 @@ int pii_reserve(struct pii_engine* e, uint32_t max_utt, uint64_t max_bytes, uint
  * needs its old and new size at once for a moment; pii_reserve up front avoids growth in the loop. */
 int pii_set_scratch_limit(struct pii_engine* e, uint64_t bytes);
 int pii_scratch_bytes(struct pii_engine* e, uint64_t* used);
-/* wait for the last device call; totals[0] = output bytes, [1] = spans, [2] = error flags */
+/* wait for the last device call; totals[0] = output bytes, [1] = spans, [2] = error flags.
+ * Two conditions are repaired here by running the call again (nothing was committed: the re-run is
+ * idempotent): a work queue that overflowed, and a row longer than two scan lanes in a scan-and-redact
+ * call that was launched without the long-row kernels.  The engine launches those only while it expects
+ * such rows: from the first call that has one until 8 calls in a row had none (a workload either has
+ * them or not; env PII_LONG_GATE=0 at creation: always).  Only the LAST enqueued call can be run again,
+ * so sync each call before the next one is enqueued -- or overwrites its buffers -- where either can
+ * happen; a call enqueued before the previous one was synced is launched on what was known then. */
 int pii_sync(struct pii_engine* e, uint64_t totals[3]);
 
 /* per-conversation context record (replaces redis GET/SETEX of context:{id}) */
@@ -220,8 +227,9 @@ int pii_last_timings_ex(struct pii_engine* e, float* ms, uint32_t n);
  * (what the roofline accounting of k_scan counts as written) */
 int pii_last_queue_sizes(struct pii_engine* e, uint64_t* pairs, uint64_t* events);
 /* the last call's work sizes: [0] candidate pairs [1] scan events [2] scan lanes [3] bytes per scan lane
- * (1 KiB for big batches, down to 128 B for small ones) [4] window-findings arena entries [5] spans;
- * fills min(n, 6) entries and returns that count */
+ * (1 KiB for big batches, down to 128 B for small ones) [4] window-findings arena entries [5] spans
+ * [6] rows cut into several lanes (scan-and-redact calls) [7] 1 if the long-row kernels were launched
+ * [8] re-runs the last pii_sync did; fills min(n, 9) entries and returns that count */
 int pii_last_stats(struct pii_engine* e, uint64_t* out, uint32_t n);
 
 /* ---------------------------------------------------------------- multi-turn window re-scan (a12)
