@@ -8,9 +8,11 @@
 //   k_chunk_index  lane -> utterance ranges of ~BYTES_PER_LANE bytes (load balance, no halo needed);
 //                  per-row defaults
 //   k_lane_bits    utterance-start words per lane and 64-byte block (lane-interleaved, coalesced)
-//   k_halo         start states of the lanes a long row's slice boundaries cut (one workgroup per row)
 //   k_scan         REVERSE two-automaton DFA scan, tables in LDS.  D = relaxed detector prefilter,
-//                  K = exact context keywords.  Emits candidate STARTS (events) per lane
+//                  K = exact context keywords.  Emits candidate STARTS (events) per lane; a lane that a
+//                  long row's slice boundary cuts steps its halo first, for its start state
+//   k_scan_fix     checks each such start state against the neighbour's real end state and re-scans the
+//                  lanes whose halo guessed wrong (one workgroup per long row)
 //   k_pairs        agent-row context group (extract_expected_pii, main.py:558-578); (start, pattern)
 //                  pair queue
 //   k_ctx_scan / k_ctx_apply   per-conversation context (Redis SETEX/GET + TTL) as a segmented scan
@@ -42,9 +44,6 @@ using namespace pii;
 namespace {
 
 constexpr int NE_MAX = 2;          // excluder patterns
-#ifndef SCAN_INLINE_HALO
-#define SCAN_INLINE_HALO 1          // k_scan steps a cut lane's halo itself (no k_halo launch per SCAN group)
-#endif
 constexpr size_t SCAN_LDS_TWO_WG = 80 * 1024;   // k_scan tables up to this: two workgroups per CU
 #ifndef SCAN1_BLOCK
 #define SCAN1_BLOCK 768
@@ -346,21 +345,17 @@ __device__ __forceinline__ uint32_t byte_c(const uint4& w) {
 // Utterance-start words, lane-interleaved: word[i * n_lanes + t] holds, for the lane in scan slot t,
 // its i-th block from the top (address-aligned 64-byte block b_top - i, b = (position + r0) >> 6):
 // bit k <=> a non-empty utterance of the lane starts at position 64b - r0 + k, or that position is
-// the lane's scan TOP (the position after its last scanned byte: the next lane's first start, the
-// batch end, or the end of a cut lane's halo), which resets the automata before the lane's last
-// byte.  All lanes of a wavefront read word i at the same iteration, so the scan's word loads are
-// coalesced.  Blocks past LANE_WORDS use a slow path.
+// the lane's scan TOP (the position after its last scanned byte, L.hi: the next lane's first start or
+// the batch end; a lane cut at hi has no top bit and starts from its halo's state), which resets the
+// automata before the lane's last byte.  All lanes of a wavefront read word i at the same iteration,
+// so the scan's word loads are coalesced.  Blocks past LANE_WORDS use a slow path.
 constexpr int LANE_WORDS = 32;
-
-// exclusive end of the bytes lane L scans (a lane cut at hi starts from the state its halo produced,
-// k_halo, instead of stepping the halo itself)
-__device__ __forceinline__ uint32_t scan_top(const Geo& g, const Lane& L) { return L.hi; }
 
 // bits of lane c's i-th block from the top (the slow path for i >= LANE_WORDS: binary search over the
 // lane's utterances; everything is re-derived from (c, i) so the scan keeps nothing live for it)
 __device__ __attribute__((noinline)) uint64_t block_bits_slow(const Geo g, uint32_t c, uint32_t i) {
     const Lane L = g_lane(g, c);
-    const uint32_t top = scan_top(g, L);
+    const uint32_t top = L.hi;
     const int64_t blk = (((int64_t)top - 1 + g.r0) >> 6) - i;
     const int64_t plo = blk * 64 - g.r0, phi = plo + 64;       // positions [plo, phi)
     uint64_t bits = 0;
@@ -394,66 +389,15 @@ __device__ __attribute__((noinline)) uint64_t block_bits_slow(const Geo g, uint3
 constexpr int LANE_NB = 128;                       // length buckets: 0 = longest (>= 127*32 B)
 __device__ __forceinline__ uint32_t lane_bucket(const Geo& g, uint32_t c) {
     const Lane L = g_lane(g, c);
-    const uint32_t len = scan_top(g, L) - min(L.lo, scan_top(g, L));
+    const uint32_t len = L.hi - min(L.lo, L.hi);
     return (uint32_t)(LANE_NB - 1) - min<uint32_t>(len >> 5, LANE_NB - 1);
 }
 
 constexpr uint32_t LANE_SORT_CHUNK = 1024;         // lanes per workgroup (4 per thread; ~1k workgroups at config 2)
 
-// k_scan2's lane split (see k_scan2 below for the design)
-static_assert(BYTES_PER_LANE == 1024, "k_scan2's word rows are sized for 1 KiB lanes");
-constexpr int HB_A = (3 * BYTES_PER_LANE) / 32 + 2;   // word rows of chain A: its half-blocks from its top
-constexpr int HB_B = 32;      // word rows of chain B (from its top, byte s - 1), stored after A's
-
-// The split of a lane for k_scan2: a non-empty utterance start s in (lo, top), not 32-byte aligned (so
-// A's last half-block holds byte s - 1), that makes the longer chain shortest; only lanes no cut
-// touches (their events and arena are the plain ones).  Returns (s - lo) | capA << 16 (capA: the arena
-// entries A may fill -- positions [s, hi - 1], one accept each, + the end-of-text events of its
-// starts), 0 = no split; kmax = half-blocks of the longer chain (the lane's k_scan2 iterations).
-template <class Off>
-__device__ __forceinline__ uint32_t choose_split(const Lane& L, uint32_t top, uint32_t r0, Off uoff, uint32_t& kmax) {
-    const int64_t hb_hi = ((int64_t)top - 1 + r0) >> 5, hb_lo = ((int64_t)L.lo + r0) >> 5;
-    int64_t best = hb_hi - hb_lo + 1, vs = -1, s = 0;
-    if (!L.clo && !L.chi && L.u0 + 1 < L.u1) {
-        int64_t sv = uoff(L.u0 + 1);
-        for (int64_t v = (int64_t)L.u0 + 1; v < (int64_t)L.u1; ++v) {
-            if (sv >= (int64_t)top) break;
-            const int64_t sn = uoff(v + 1);
-            if (sv > (int64_t)L.lo && ((sv + r0) & 31) != 0 && sn != sv) {
-                const int64_t hs = (sv + r0) >> 5;
-                const int64_t na = hb_hi - hs + 1, nb = hs - hb_lo + 1, mx = max(na, nb);
-                if (na <= HB_A && nb <= HB_B && mx < best) {
-                    best = mx;
-                    vs = v;
-                    s = sv;
-                }
-            }
-            sv = sn;
-        }
-    }
-    kmax = (uint32_t)best;
-    if (vs < 0) return 0;
-    const int64_t cap = ((int64_t)top - s) + ((int64_t)L.u1 - vs);
-    if (s - (int64_t)L.lo >= 65536 || cap >= 65536) {
-        kmax = (uint32_t)(hb_hi - hb_lo + 1);
-        return 0;
-    }
-    return (uint32_t)(s - L.lo) | (uint32_t)cap << 16;
-}
-
-// the longer chain's half-blocks of lane L with split sp (the k_scan2 lane order's key)
-__device__ __forceinline__ uint32_t split_kmax(const Lane& L, uint32_t top, uint32_t r0, uint32_t sp) {
-    const uint32_t hb_hi = (top - 1 + r0) >> 5, hb_lo = (L.lo + r0) >> 5;
-    if (!sp) return hb_hi - hb_lo + 1;
-    const uint32_t hs = (L.lo + (sp & 0xffffu) + r0) >> 5;
-    return max(hb_hi - hs + 1, hs - hb_lo + 1);
-}
-
-// also records every lane's geometry (g.lanes is null here; later kernels read the records); SPLIT
-// (k_scan2): also each lane's split (spl), and the lanes are ordered by the longer chain's length
-template <bool SPLIT>
+// also records every lane's geometry (g.lanes is null here; later kernels read the records)
 __global__ __launch_bounds__(256) void k_lane_count(const Geo g, uint32_t* __restrict__ bucket_cnt,
-                                                    uint4* __restrict__ lanes, uint32_t* __restrict__ spl) {
+                                                    uint4* __restrict__ lanes) {
     __shared__ uint32_t h[LANE_NB];
     for (int i = threadIdx.x; i < LANE_NB; i += blockDim.x) h[i] = 0;
     __syncthreads();
@@ -462,13 +406,7 @@ __global__ __launch_bounds__(256) void k_lane_count(const Geo g, uint32_t* __res
         const Lane L = g_lane_slow(g, c);
         lanes[c] = lane_pack(L);
         const uint32_t len = L.hi - min(L.lo, L.hi);
-        uint32_t key = len >> 5;
-        if constexpr (SPLIT) {
-            uint32_t km = 0;
-            spl[c] = len ? choose_split(L, L.hi, g.r0, [&](int64_t u) { return g_off(g, (uint32_t)u); }, km) : 0u;
-            key = len ? km : 0u;
-        }
-        const uint32_t bk = (uint32_t)(LANE_NB - 1) - min(key, (uint32_t)(LANE_NB - 1));
+        const uint32_t bk = (uint32_t)(LANE_NB - 1) - min(len >> 5, (uint32_t)(LANE_NB - 1));
         atomicAdd(&h[bk], 1u);
     }
     __syncthreads();
@@ -477,10 +415,8 @@ __global__ __launch_bounds__(256) void k_lane_count(const Geo g, uint32_t* __res
 }
 
 // bucket_cnt[0..NB) = counts (k_lane_count), bucket_cnt[NB..2NB) = reservation cursors (zeroed)
-template <bool SPLIT>
 __global__ __launch_bounds__(256) void k_lane_place(const Geo g, uint32_t* __restrict__ bucket_cnt,
-                                                    uint32_t* __restrict__ lane_perm, uint32_t* __restrict__ lane_pos,
-                                                    const uint32_t* __restrict__ spl) {
+                                                    uint32_t* __restrict__ lane_perm, uint32_t* __restrict__ lane_pos) {
     constexpr int PER = LANE_SORT_CHUNK / 256;
     __shared__ uint32_t base[LANE_NB], h[LANE_NB];
     if (threadIdx.x < 64) {                        // exclusive prefix of the counts, one wavefront
@@ -504,15 +440,7 @@ __global__ __launch_bounds__(256) void k_lane_place(const Geo g, uint32_t* __res
     for (int j = 0; j < PER; ++j) {
         const uint32_t c = c0 + j * 256 + threadIdx.x;
         bk[j] = 0;
-        if (c < g.n_chunks) {
-            if constexpr (SPLIT) {
-                const Lane L = g_lane(g, c);
-                const uint32_t key = L.hi > L.lo ? split_kmax(L, L.hi, g.r0, spl[c]) : 0u;
-                bk[j] = (uint32_t)(LANE_NB - 1) - min(key, (uint32_t)(LANE_NB - 1));
-            } else {
-                bk[j] = lane_bucket(g, c);
-            }
-        }
+        if (c < g.n_chunks) bk[j] = lane_bucket(g, c);
         rk[j] = c < g.n_chunks ? atomicAdd(&h[bk[j]], 1u) : 0u;
     }
     __syncthreads();
@@ -544,7 +472,7 @@ __device__ __forceinline__ uint32_t scan_state(uint32_t nd, uint32_t nk) { retur
 
 // The state a lane cut at hi starts from: both automata stepped right to left over the SCAN_HALO
 // bytes after the cut (clamped to the row) from the start state, with the tables in LDS in k_scan's
-// layout (k_halo stages them); k_scan_fix verifies the result against the neighbour's real state.
+// layout (k_scan, the caller, staged them); k_scan_fix verifies the result against the neighbour's real state.
 // The halo is read as aligned 16-byte chunks (each holds a batch byte, as k_scan's reads do), the
 // bytes taken from registers: per-byte loads from 64 lanes' distant rows thrashed L2.
 __device__ uint32_t halo_state(const RulesDev& R, const Geo& g, const uint8_t* __restrict__ text, const Lane& L) {
@@ -575,39 +503,6 @@ __device__ uint32_t halo_state(const RulesDev& R, const Geo& g, const uint8_t* _
         if (a == a_lo) break;
     }
     return scan_state(nd, nk);
-}
-
-// Halo states of every cut lane, one workgroup per long row (the k_scan_fix grid), the group's scan
-// tables staged in LDS: the lanes (ca, kb] continue long row r, so lanes [ca, kb) are cut at hi.
-// Only long rows have cut lanes, so a batch without them costs one early exit.
-constexpr int HALO_BLOCK = 1024;    // k_halo: lanes of a long row in flight per workgroup (one per CU)
-__global__ __launch_bounds__(HALO_BLOCK) void k_halo(const RulesDev R, const Geo g, const uint8_t* __restrict__ text,
-                                              const uint32_t* __restrict__ long_rows,
-                                              const uint32_t* __restrict__ long_count,
-                                              uint32_t* __restrict__ lane_st, const uint32_t* __restrict__ err) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem32[];
-    const uint32_t nrows = *long_count;
-    if (blockIdx.x >= nrows || (*err & (ERR_ARGS | ERR_STITCH))) return;
-    {
-        const int nd_words = R.SD * R.CDs / 2, nk_words = R.SK * R.CKs / 2;
-        const uint32_t* g_td = reinterpret_cast<const uint32_t*>(R.td);
-        const uint32_t* g_tk = reinterpret_cast<const uint32_t*>(R.tk);
-        uint32_t* d_td = smem32 + SCAN_TD_BASE / 4;
-        uint32_t* d_tk = d_td + nd_words;
-        for (int i = threadIdx.x; i < 256; i += blockDim.x) smem32[i] = R.cmap4[i];
-        for (int i = threadIdx.x; i < nd_words; i += blockDim.x) d_td[i] = g_td[i];
-        for (int i = threadIdx.x; i < nk_words; i += blockDim.x) d_tk[i] = g_tk[i];
-    }
-    __syncthreads();
-    for (uint32_t ri = blockIdx.x; ri < nrows; ri += gridDim.x) {
-        uint32_t ca, kb;
-        int64_t s_r, e_r;
-        row_lanes(g, long_rows[ri], ca, kb, s_r, e_r);
-        for (uint32_t c = ca + threadIdx.x; c < kb; c += blockDim.x) {
-            const Lane L = g_lane(g, c);
-            if (L.chi && scan_top(g, L) > L.lo) lane_st[2 * c] = halo_state(R, g, text, L);
-        }
-    }
 }
 
 // The utterance offsets of a wavefront's 64 lanes, staged in LDS as 16-bit offsets from the start of
@@ -658,7 +553,7 @@ __global__ __launch_bounds__(256) void k_lane_bits(const Geo g, const uint32_t* 
     if (c >= g.n_chunks) return;
     auto uoff = [&](int64_t u) { return W.off(g, (uint32_t)u); };
     const Lane L = g_lane(g, c);
-    const uint32_t top = scan_top(g, L);
+    const uint32_t top = L.hi;
     if (top <= L.lo) return;
     const int64_t b_hi = ((int64_t)top - 1 + g.r0) >> 6, b_lo = ((int64_t)L.lo + g.r0) >> 6;
     const int64_t nw = min<int64_t>(b_hi - b_lo + 1, LANE_WORDS);
@@ -698,10 +593,9 @@ __device__ __forceinline__ void scan_emit(Event* __restrict__ ev, uint32_t ab, u
 
 // The lane's (start, pattern) pair count, summed where its events are born (lane_np, the pair queue's
 // layout key: the count pass k_pairs_flat<false> re-read every event from HBM for this sum).  Called
-// after the scan loop by the thread that wrote the events (program order; k_scan2 moves its B events the
-// same way): no accumulator is held across the loop (summing in scan_emit would cost a VGPR there, and
-// k_scan sits at its 80-VGPR budget), and the re-reads hit the lines the thread just stored.  An empty
-// lane counts 0.
+// after the scan loop by the thread that wrote the events (program order): no accumulator is held
+// across the loop (summing in scan_emit would cost a VGPR there, and k_scan sits at its 80-VGPR
+// budget), and the re-reads hit the lines the thread just stored.  An empty lane counts 0.
 __device__ __forceinline__ uint32_t lane_pairs(const RulesDev& R, const Event* ev, uint32_t ab, uint32_t cnt) {
     // eight events per round, their loads issued together and then their counts' (clamped to the lane's
     // last event, so every load is one of its own records) instead of one event after the other, each
@@ -890,7 +784,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == SCAN_B
     const Lane L = g_lane(g, c);
     // positions relative to the batch base fit 32 bits (PII_MAX_BATCH_BYTES); 32-bit arithmetic keeps
     // the lane's bookkeeping small (VGPRs decide this kernel's occupancy)
-    const uint32_t top = scan_top(g, L);
+    const uint32_t top = L.hi;
     const uint32_t end_r = (uint32_t)g_off(g, g.n_utt);
     uint32_t cnt = 0;
     if (top > L.lo) {
@@ -903,15 +797,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == SCAN_B
         // "previous byte started an utterance": start rows; a lane cut at hi continues from its halo state
         uint32_t nd = 0, nk = 0, pm = 0xffffffffu;
         if (L.chi) {
-#if SCAN_INLINE_HALO
             // the lane's start state: its halo stepped here, from the tables already in LDS (a cut
             // lane is rare except in long rows, where every lane pays 128 of its 1024 steps); the
             // guess is kept for k_scan_fix, which checks it against the neighbour's real end state
             const uint32_t hs = halo_state(R, g, text, L);
             lane_st[2 * c] = hs;
-#else
-            const uint32_t hs = lane_st[2 * c];
-#endif
             nd = hs & 0xffffu;
             nk = hs >> 16;
             pm = 0;
@@ -952,303 +842,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == SCAN_B
     }
     lane_cnt[c] = cnt;
     if (lane_np) lane_np[c] = lane_pairs(R, ev, (uint32_t)ev_base(L, c), cnt);
-}
-
-// ------------------------------------------------------------------ k_scan2: two chains per lane
-// k_scan is bound by one dependent LDS read per byte per lane (the D row of byte j is the entry read
-// at byte j + 1): at the 6 waves/SIMD its VGPRs allow, 4.7 achieved, the CU's LDS idles between a
-// wave's dependent reads (issue-active 24%, parked 39%).  k_scan2 gives each lane TWO independent
-// chains.  k_lane_bits2 SPLITS a lane at one of its own utterance starts s near its middle: chain A
-// steps [s, top) exactly as k_scan steps a lane [s, top), chain B steps [lo, s) from the start state --
-// which is the single chain's state after it steps byte s (an utterance start resets both automata),
-// so the split needs no halo and no verification, and the events are exactly the single chain's.
-// The chains step interleaved, byte for byte, over 32-byte half-blocks (a block of text per chain
-// in flight, as k_scan).  A keeps the events at positions >= s, B those < s (a position is reported
-// by the step over the byte before it: A's last half-block holds byte s - 1, as s is not 32-byte
-// aligned).  A writes into the lane's arena, B behind A's capacity; B's events are moved down behind
-// A's at the end, so the arena holds the single chain's events in its order and no consumer changes.
-// A lane without a usable utterance start (a cut lane, one long utterance) runs chain A alone.
-// Register budget (80 VGPRs: 6 waves/SIMD in 768-thread workgroups, two per CU): per byte and chain
-// one history word (both automata's rows, masked, packed; the emission re-derives the byte's class
-// from the text) instead of k_scan's ad / ak, and per chain two 16-byte chunks of text, ping-pong: the
-// next chunk is loaded as soon as the one in its registers has been stepped (no register copies, which
-// would wait for the loads they copy), 16 bytes per chain = 32 interleaved steps ahead of its use.
-// Word rows: k_scan2 runs for 1 KiB lanes with rows longer than 2 KiB cut (long_min), so a lane is
-// shorter than 3 KiB and A's half-blocks always fit HB_A rows -- the loop needs no slow path, and its
-// prefetch is branch-free (a finished chain re-reads its last half-block), so the compiler's counted
-// vmcnt waits stay a whole half-block behind the loads.
-// split[slot] = the lane's split (spl, by lane: k_lane_count); words32 rows [0, HB_A) = A's
-// half-blocks from the lane's top, rows [HB_A, HB_A + HB_B) = B's from byte s - 1
-__global__ __launch_bounds__(256) void k_lane_bits2(const Geo g, const uint32_t* __restrict__ lane_pos,
-                                                    const uint32_t* __restrict__ spl, uint32_t* __restrict__ words,
-                                                    uint32_t* __restrict__ split) {
-    __shared__ uint16_t s_off[4][WROWS_CAP];
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t cw0 = c - lane;
-    const uint32_t cw1 = min(cw0 + 64, g.n_chunks);
-    WaveRows W;
-    if (cw0 < g.n_chunks) W.stage(g, cw0, cw1, lane, s_off[wv]);
-    __syncthreads();
-    if (c >= g.n_chunks) return;
-    auto uoff = [&](int64_t u) { return W.off(g, (uint32_t)u); };
-    const Lane L = g_lane(g, c);
-    const uint32_t top = scan_top(g, L);
-    if (top <= L.lo) return;                 // (k_scan2 reads nothing of an empty lane)
-    const uint32_t slot = lane_pos[c];
-    const uint64_t n = g.n_chunks;
-    const int64_t r0 = g.r0;
-    const int64_t vmin = (int64_t)L.u0 + (L.clo ? 1 : 0);
-    const int64_t hb_hi = ((int64_t)top - 1 + r0) >> 5, hb_lo = ((int64_t)L.lo + r0) >> 5;
-    const uint32_t sp = spl[c];
-    split[slot] = sp;
-    auto rows = [&](int64_t h0, int64_t nw, int64_t v, uint64_t row0, bool with_top) {
-        int64_t sv = v >= vmin ? uoff(v) : 0;
-        for (int64_t i = 0; i < nw; ++i) {
-            const int64_t plo = (h0 - i) * 32 - r0;
-            uint32_t bits = 0;
-            if (with_top && i == 0 && (int64_t)top >= plo && (int64_t)top < plo + 32) bits |= 1u << (top - plo);
-            while (v >= vmin && sv >= plo) {
-                if (sv < plo + 32 && uoff(v + 1) > sv) bits |= 1u << (sv - plo);
-                --v;
-                if (v >= vmin) sv = uoff(v);
-            }
-            words[(row0 + (uint64_t)i) * n + slot] = bits;
-        }
-    };
-    if (!sp) {
-        rows(hb_hi, min<int64_t>(hb_hi - hb_lo + 1, HB_A), (int64_t)L.u1 - 1, 0, !L.chi);
-        return;
-    }
-    // the utterance starting at s: the last one starting at or before it (a binary search of its rows)
-    const int64_t s = (int64_t)L.lo + (sp & 0xffffu);
-    int64_t a = vmin, b = (int64_t)L.u1 - 1;
-    while (a < b) {
-        const int64_t m = (a + b + 1) >> 1;
-        if (uoff(m) <= s) a = m;
-        else b = m - 1;
-    }
-    const int64_t hs = (s + r0) >> 5;
-    rows(hb_hi, hb_hi - hs + 1, (int64_t)L.u1 - 1, 0, !L.chi);
-    rows(hs, hs - hb_lo + 1, a, HB_A, false);
-}
-
-// the events of one chain's 8-byte group (scan_emit8's order); h[j] = the masked rows byte j was
-// stepped from (HK: D | K << 16, the class re-derived from the group's text dwords; else the D address)
-template <bool HK>
-__device__ __forceinline__ void scan2_emit8(Event* __restrict__ ev, uint32_t ab, uint32_t& cnt, uint32_t m,
-                                            const uint32_t (&h)[8], uint32_t w_lo, uint32_t w_hi, uint32_t p0,
-                                            uint32_t lo_r, uint32_t len_r, uint32_t tk_base, uint32_t eot_d,
-                                            uint32_t eot_k, uint32_t dsh) {
-    do {
-        const uint32_t b = (uint32_t)__builtin_ctz(m);
-        m &= m - 1u;
-        const uint32_t j = 7u - (b >> 1);
-        const uint32_t hj = sel8(h, j);
-        uint32_t a, k;
-        if (HK) {
-            const uint32_t by = (((j & 4u) ? w_hi : w_lo) >> (8u * (j & 3u))) & 0xffu;
-            const uint32_t cw = *reinterpret_cast<const __attribute__((address_space(3))) uint32_t*>((size_t)(4u * by));
-            a = (hj & 0xffffu) + (cw & 0xffffu);
-            k = (hj >> 16) + (cw >> 16);
-        } else {
-            a = hj;
-            k = tk_base;
-        }
-        uint32_t pos = p0 + j + 1u;
-        if (b & 1u) {
-            a = ((lds_u16(a) & 0xfffcu) << dsh) + eot_d;
-            k = (lds_u16(k) & 0xfffcu) + eot_k;
-            pos -= 1u;
-        }
-        scan_emit(ev, ab, cnt, pos, lo_r, len_r, a, k, tk_base);
-    } while (m);
-}
-
-// one byte of chain X (J: byte of the group, BIT: its bit in the half-block word)
-#define S2_STEP1(X, J, BIT)                                                                       \
-    {                                                                                             \
-        if (HK) {                                                                                 \
-            h##X[J] = ((nk##X << 16) | nd##X) & ~pm##X & 0xfffcfffcu;                             \
-            uint32_t ad_, ak_;                                                                    \
-            asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_0" \
-                : "=v"(ad_) : "v"(h##X[J]), "v"(c##X[J]));                                       \
-            asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1" \
-                : "=v"(ak_) : "v"(h##X[J]), "v"(c##X[J]));                                       \
-            nd##X = lds_u16(ad_);                                                                 \
-            nk##X = lds_u16(ak_);                                                                 \
-            m##X = __builtin_amdgcn_alignbit(nd##X | nk##X, m##X, 2);                             \
-        } else {                                                                                  \
-            h##X[J] = ((nd##X & ~pm##X & 0xfffcu) << dsh) + c##X[J];                              \
-            nd##X = lds_u16(h##X[J]);                                                             \
-            m##X = __builtin_amdgcn_alignbit(nd##X, m##X, 2);                                     \
-        }                                                                                         \
-        asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(pm##X) : "v"(b##X), "n"(BIT));                      \
-    }
-
-#define S2_CLASSES8(C, W, H)                                                                      \
-    C[0] = class_of<(H) + 0>(W);                                                                  \
-    C[1] = class_of<(H) + 1>(W);                                                                  \
-    C[2] = class_of<(H) + 2>(W);                                                                  \
-    C[3] = class_of<(H) + 3>(W);                                                                  \
-    C[4] = class_of<(H) + 4>(W);                                                                  \
-    C[5] = class_of<(H) + 5>(W);                                                                  \
-    C[6] = class_of<(H) + 6>(W);                                                                  \
-    C[7] = class_of<(H) + 7>(W);
-
-#define S2_STEP2(J, BIT) S2_STEP1(A, J, BIT) S2_STEP1(B, J, BIT)
-
-// one 8-byte group of both chains: bytes H..H+7 of chunk WA / WB, at bit OFF + H of the words
-#define S2_GROUP(WA, WB, H, OFF)                                                                  \
-    {                                                                                             \
-        uint32_t cA[8], cB[8], hA[8], hB[8], mA = 0, mB = 0;                                      \
-        S2_CLASSES8(cA, WA, H)                                                                    \
-        S2_CLASSES8(cB, WB, H)                                                                    \
-        const uint32_t mkA = aliveA ? lds_u16(spread + 2u * ((bA >> ((OFF) + (H))) & 0xffu)) : 0u; \
-        const uint32_t mkB = aliveB ? lds_u16(spread + 2u * ((bB >> ((OFF) + (H))) & 0xffu)) : 0u; \
-        S2_STEP2(7, (OFF) + (H) + 7) S2_STEP2(6, (OFF) + (H) + 6)                                 \
-        S2_STEP2(5, (OFF) + (H) + 5) S2_STEP2(4, (OFF) + (H) + 4)                                 \
-        S2_STEP2(3, (OFF) + (H) + 3) S2_STEP2(2, (OFF) + (H) + 2)                                 \
-        S2_STEP2(1, (OFF) + (H) + 1) S2_STEP2(0, (OFF) + (H) + 0)                                 \
-        mA = (mA >> 16) & mkA;                                                                    \
-        mB = (mB >> 16) & mkB;                                                                    \
-        if (__builtin_expect((mA | mB) != 0, 0)) {                                                \
-            if (mA)                                                                               \
-                scan2_emit8<HK>(ev, abA, cntA, mA, hA, (H) ? WA.z : WA.x, (H) ? WA.w : WA.y,       \
-                                bposA + (OFF) + (H), sA, ehi - sA, tk_base, eot_d, eot_k, dsh);   \
-            if (mB)                                                                               \
-                scan2_emit8<HK>(ev, abB, cntB, mB, hB, (H) ? WB.z : WB.x, (H) ? WB.w : WB.y,       \
-                                bposB + (OFF) + (H), lo_r, sA - 1u - lo_r, tk_base, eot_d, eot_k, dsh); \
-        }                                                                                         \
-    }
-
-#ifndef SCAN2_BLOCK
-#define SCAN2_BLOCK 768
-#endif
-#ifndef SCAN2_WAVES
-#define SCAN2_WAVES 6
-#endif
-template <bool HK, int NT = SCAN2_BLOCK>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == SCAN2_BLOCK ? SCAN2_WAVES : 4, NT == SCAN2_BLOCK ? SCAN2_WAVES : 4))) void k_scan2(
-    const RulesDev R, const Geo g, const uint8_t* __restrict__ text, const uint32_t* __restrict__ words,
-    const uint32_t* __restrict__ split, const uint32_t* __restrict__ lane_perm, Event* __restrict__ ev,
-    uint32_t* __restrict__ lane_cnt, uint32_t* __restrict__ lane_st, const uint32_t* __restrict__ err,
-    uint32_t* __restrict__ lane_np) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem32[];
-    if (*err & ERR_ARGS) return;
-    const int nd_words = R.SD * R.CDs / 2;
-    const int nk_words = R.SK * R.CKs / 2;
-    const uint32_t tk_base = SCAN_TD_BASE + (uint32_t)nd_words * 4;
-    {
-        const uint32_t* g_td = reinterpret_cast<const uint32_t*>(R.td);
-        const uint32_t* g_tk = reinterpret_cast<const uint32_t*>(R.tk);
-        uint32_t* d_td = smem32 + SCAN_TD_BASE / 4;
-        uint32_t* d_tk = d_td + nd_words;
-        for (int i = threadIdx.x; i < 256; i += blockDim.x) smem32[i] = R.cmap4[i];
-        for (int i = threadIdx.x; i < nd_words; i += blockDim.x) d_td[i] = g_td[i];
-        for (int i = threadIdx.x; i < nk_words; i += blockDim.x) d_tk[i] = g_tk[i];
-        uint32_t* d_sp = d_tk + nk_words;
-        for (int i = threadIdx.x; i < 128; i += blockDim.x) d_sp[i] = scan_spread(2 * i) | scan_spread(2 * i + 1) << 16;
-    }
-    __syncthreads();
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;      // slot (lanes longest first)
-    if (t >= g.n_chunks) return;
-    const uint32_t c = lane_perm[t];
-    const Lane L = g_lane(g, c);
-    const uint32_t top = scan_top(g, L);
-    const uint32_t end_r = (uint32_t)g_off(g, g.n_utt);
-    uint32_t cnt = 0;
-    if (top > L.lo) {
-        uint32_t lo_r, len_r;
-        emit_range(L, lo_r, len_r);
-        const uint32_t ab = (uint32_t)ev_base(L, c);
-        const uint32_t eot_d = SCAN_TD_BASE + 2u * (uint32_t)(R.CD - 1), eot_k = tk_base + 2u * (uint32_t)(R.CK - 1);
-        const uint32_t spread = tk_base + (uint32_t)nk_words * 4;
-        const uint32_t dsh = HK ? 0u : (uint32_t)R.dsh;
-        const uint32_t sp = split[t];
-        const uint32_t s = L.lo + (sp & 0xffffu);        // (lo when not split)
-        const uint32_t abA = ab, abB = ab + (sp >> 16);
-        // emission ranges: A [sA, ehi] ([s, e_hi] when split, the lane's own otherwise), B [lo_r, s - 1]
-        const uint32_t sA = sp ? s : lo_r, ehi = lo_r + len_r;
-        uint32_t ndA = 0, nkA = 0, pmA = 0xffffffffu, ndB = 0, nkB = 0, pmB = 0xffffffffu;
-        if (L.chi) {             // (never split)
-#if SCAN_INLINE_HALO
-            const uint32_t hs = halo_state(R, g, text, L);
-            lane_st[2 * c] = hs;
-#else
-            const uint32_t hs = lane_st[2 * c];
-#endif
-            ndA = hs & 0xffffu;
-            nkA = hs >> 16;
-            pmA = 0;
-        }
-        const uint32_t r0 = g.r0;
-        const uintptr_t tpb = (uintptr_t)(text + g.base) - r0;
-        const uint32_t hbA = (top - 1 + r0) >> 5, hb_lo = (L.lo + r0) >> 5;
-        const uint32_t hs = sp ? (s + r0) >> 5 : hb_lo;
-        const uint32_t nA = hbA - hs + 1, nB = sp ? hs - hb_lo + 1 : 0, hbB = hs;
-        const uint32_t q_end = (end_r - 1 + r0) >> 4;             // last chunk with a batch byte
-        const uint32_t n = g.n_chunks;           // (word rows * lanes < 2^32: rows < 2^8, lanes < 2^23)
-        // the top half-block: its upper chunk only when it holds a batch byte (then every load is
-        // unconditional: a finished chain re-reads its last half-block, its start bits forced to ones;
-        // a chunk past the batch end is never read -- a top half-block's upper chunk is replaced by its
-        // lower one, whose bytes then step only as garbage of a finished chain)
-        // (uniform base + 32-bit offsets: the loads take the SGPR-base form, no 64-bit address VGPRs)
-        const uint8_t* const tbase = reinterpret_cast<const uint8_t*>(tpb);
-        auto ld = [&](uint32_t off) { return gload16_at(tbase, off); };
-        auto hi16 = [&](uint32_t hb) { return hb * 32u + (2 * hb + 1 <= q_end ? 16u : 0u); };
-        auto lo16 = [&](uint32_t hb) { return hb * 32u; };
-        uint4 PA = make_uint4(0, 0, 0, 0);
-        if (2 * hbA + 1 <= q_end) PA = ld(lo16(hbA) + 16);
-        uint4 QA = ld(lo16(hbA)), PB = ld(hi16(hbB)), QB = ld(lo16(hbB));
-        // (the lane's counts are re-derived per use: registers decide this kernel's occupancy)
-#define LAST_A (nA - 1)
-#define LAST_B (nB ? nB - 1 : 0u)
-        uint32_t wA = words[t], wB = words[(uint32_t)HB_A * n + t];
-        uint32_t nwA = words[min(1u, LAST_A) * n + t], nwB = words[(HB_A + min(1u, LAST_B)) * n + t];
-        uint32_t cntA = 0, cntB = 0;
-        for (uint32_t k = 0;; ++k) {
-            const bool aliveA = k < nA, aliveB = k < nB;      // (lane masks: no VGPRs)
-            const uint32_t bA = aliveA ? wA : 0xffffffffu, bB = aliveB ? wB : 0xffffffffu;
-            const uint32_t ka = min(k + 1, LAST_A), kb = min(k + 1, LAST_B);
-            const uint32_t bposA = 32u * (hbA - k) - r0, bposB = 32u * (hbB - k) - r0;
-            S2_GROUP(PA, PB, 8, 16)
-            S2_GROUP(PA, PB, 0, 16)
-            PA = ld(hi16(hbA - ka));
-            PB = ld(hi16(hbB - kb));
-            S2_GROUP(QA, QB, 8, 0)
-            S2_GROUP(QA, QB, 0, 0)
-            QA = ld(lo16(hbA - ka));
-            QB = ld(lo16(hbB - kb));
-            wA = nwA;
-            wB = nwB;
-            nwA = words[min(k + 2, LAST_A) * n + t];
-            nwB = words[(HB_A + min(k + 2, LAST_B)) * n + t];
-            if (k + 1 >= max(nA, nB)) break;
-        }
-#undef LAST_A
-#undef LAST_B
-        // (the lane's id and cut flag re-read: nothing but the chains' state stays live across the loop)
-        if (g.lanes[lane_perm[t]].z >> 31)                              // cut at lo: never split,
-            lane_st[2 * lane_perm[t] + 1] = scan_state(ndA, nkA);       // A ended at byte lo
-        if (cntB && abA + cntA < abB) {         // B's events behind A's (ascending: the target is lower)
-            const uint2* src = reinterpret_cast<const uint2*>(ev + abB);
-            uint2* dst = reinterpret_cast<uint2*>(ev + abA + cntA);
-            for (uint32_t i = 0; i < cntB; i += 4) {
-                uint2 x[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (i + r < cntB) x[r] = src[i + r];
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (i + r < cntB) dst[i + r] = x[r];
-            }
-        }
-        cnt = cntA + cntB;
-    }
-    lane_cnt[lane_perm[t]] = cnt;
-    // (B's events sit behind A's by now: the arena holds the lane's cnt events from its base)
-    if (lane_np) lane_np[lane_perm[t]] = lane_pairs(R, ev, (uint32_t)ev_base(g_lane(g, lane_perm[t]), lane_perm[t]), cnt);
 }
 
 // ---- k_scan_fix: stitching of cut rows.  A lane cut at hi scanned SCAN_HALO bytes past the cut from
@@ -1305,11 +898,6 @@ constexpr int FIX_Q = 512;
 // LDS past the scan tables (the tables' entries are absolute LDS addresses, so the kernel declares no
 // static LDS): queue, entry states, previous round's lanes, counters
 constexpr size_t FIX_LDS = (3 * FIX_Q + 4) * 4;
-#if !SCAN_INLINE_HALO && defined(SCAN_STREAMS) && SCAN_STREAMS > 1
-// k_halo of group q runs on the engine stream after the fork; k_scan of that group on an aux stream
-// that waits only on the fork: the scan would read halo states before k_halo writes them
-#error "SCAN_STREAMS > 1 needs SCAN_INLINE_HALO (k_scan steps its own halo)"
-#endif
 #ifndef SCAN_STREAMS
 #define SCAN_STREAMS 3                // streams for several SCAN groups' passes (config 5, wall per step, one box:
                                       // 1 / 2 / 3 -> 6.65 / 6.31 / 6.28 ms)
@@ -5256,9 +4844,6 @@ struct pii_engine {
     uint32_t* lane_bkt = nullptr;      // [2 * LANE_NB] bucket counts + reservation cursors
     uint32_t* lane_cnt = nullptr;
     uint64_t* bnd = nullptr;
-    uint32_t* lane_split = nullptr;    // k_scan2: per slot split point | A's arena capacity (k_lane_bits2)
-    uint32_t* lane_spl = nullptr;      // the same per lane (k_lane_count)
-    bool scan2 = false;                // two chains per lane in the SCAN (PII_SCAN2=1: k_scan2; slower)
     bool scan_count = true;            // the scan kernels count each lane's pairs (PII_SCAN_COUNT=0: the count pass does)
     // The long-row gate (launch_front): whether a workload has rows that get cut is a property of the
     // workload, not of one batch, so a scan-and-redact call launches the long-row kernels only while cut
@@ -5478,11 +5063,7 @@ int ensure_scratch(pii_engine* e, uint32_t n_utt, uint64_t bytes, uint32_t n_lan
         if ((rc = grow(e, e->lane_cnt, nl * e->n_sg))) return rc;
         if (e->n_sg > 1 && (rc = grow(e, e->lane_evn, nl))) return rc;
         if ((rc = grow(e, e->lane_ev, nl))) return rc;
-        // utterance-start words: k_scan's u64 per block (LANE_WORDS rows) or k_scan2's u32 per
-        // half-block (HB_A + HB_B rows), one buffer for either
-        if ((rc = grow(e, e->bnd, nl * std::max<uint64_t>(LANE_WORDS, (HB_A + HB_B) / 2)))) return rc;
-        if ((rc = grow(e, e->lane_split, nl))) return rc;
-        if ((rc = grow(e, e->lane_spl, nl))) return rc;
+        if ((rc = grow(e, e->bnd, nl * LANE_WORDS))) return rc;     // utterance-start words (k_lane_bits)
         if ((rc = grow(e, e->lane_pair, nl))) return rc;
         if ((rc = grow(e, e->lane_np, nl))) return rc;
         if ((rc = grow(e, e->lane_st, 2 * nl * e->n_sg))) return rc;
@@ -5647,7 +5228,7 @@ size_t hist_bytes(const pii_engine* e) { return 64 + (size_t)std::max(e->R.T, 25
 
 // The stages every call shares: lane index, reverse DFA scan (+ the stitching of cut rows), (start,
 // pattern) pair queue, context (segmented scan), leftmost-first confirmation.  Records tev[0..2].
-// long_kernels = false (the long-row gate is closed): k_fill_long, k_halo and k_scan_fix are not launched,
+// long_kernels = false (the long-row gate is closed): k_fill_long and k_scan_fix are not launched,
 // and k_chunk_index fails the call with ERR_LONG if it meets a cut row after all.
 constexpr uint32_t LONG_IDLE_CALLS = 8;      // calls without a cut row after which the gate closes again
 int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint32_t n_utt, uint32_t n_chunks,
@@ -5675,18 +5256,12 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
             k_fill_long<<<row_grid(e, total_bytes), 256, 0, st>>>(offs, n_utt, n_chunks, e->lane_shift, e->r0, e->long_rows,
                                                                    e->long_count, (uint32_t)e->cap_long, e->first_utt);
         if (n_chunks > 0) {
-            // two chains per lane (k_scan2) for batches of full-size lanes; small batches (a re-scan
-            // step: 128-512-byte lanes of one or two rows) have no utterance start to split at
-            const bool split = e->scan2 && e->lane_shift == (uint32_t)__builtin_ctz(BYTES_PER_LANE) &&
-                               e->long_min != NO_CUTS && e->n_sg == 1;
             const uint32_t nsb = (n_chunks + LANE_SORT_CHUNK - 1) / LANE_SORT_CHUNK;
             Geo g0 = g;
             g0.lanes = nullptr;
-            (split ? k_lane_count<true> : k_lane_count<false>)<<<nsb, 256, 0, st>>>(g0, e->lane_bkt, e->lane_geo,
-                                                                                    e->lane_spl);
-            (split ? k_lane_place<true> : k_lane_place<false>)<<<nsb, 256, 0, st>>>(g, e->lane_bkt, e->lane_perm,
-                                                                                    e->lane_pos, e->lane_spl);
-            // one pass per SCAN group (one for the shipped rules): halo states, scan, stitching; the
+            k_lane_count<<<nsb, 256, 0, st>>>(g0, e->lane_bkt, e->lane_geo);
+            k_lane_place<<<nsb, 256, 0, st>>>(g, e->lane_bkt, e->lane_perm, e->lane_pos);
+            // one pass per SCAN group (one for the shipped rules): scan, then the stitching; the
             // utterance-start words are written once.  Several groups: group q on stream q mod
             // SCAN_STREAMS (forked after the words, joined before the pairs), so one pass's tail -- the
             // last workgroups of its longest-first lanes -- overlaps the next passes.
@@ -5704,16 +5279,8 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                 Event* evq = e->ev + (uint64_t)q * e->cap_ev;
                 uint32_t* cq = e->lane_cnt + (uint64_t)q * e->cap_lanes;
                 uint32_t* stq = e->lane_st + 2ull * q * e->cap_lanes;
-                if (q == 0 && split)
-                    k_lane_bits2<<<(n_chunks + 255) / 256, 256, 0, st>>>(g, e->lane_pos, e->lane_spl,
-                                                                         reinterpret_cast<uint32_t*>(e->bnd),
-                                                                         e->lane_split);
-                else if (q == 0)
-                    k_lane_bits<<<(n_chunks + 255) / 256, 256, 0, st>>>(g, e->lane_pos, e->bnd);
-                if (!SCAN_INLINE_HALO && long_k)
-                    k_halo<<<row_grid(e, total_bytes), HALO_BLOCK, e->sg_lds[q], st>>>(Rq, g, text, e->long_rows,
-                                                                                  e->long_count, stq, e->d_err);
                 if (q == 0) {
+                    k_lane_bits<<<(n_chunks + 255) / 256, 256, 0, st>>>(g, e->lane_pos, e->bnd);
                     if (e->timing >= 1) HIPCHK(hipEventRecord(e->kev[0], st));
                     if (two) {
                         HIPCHK(hipEventRecord(e->ev_fork, st));
@@ -5727,18 +5294,10 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                 // table); only the dictionary groups' ~100 KB tables need one 1024-thread workgroup
                 const bool one_wg = e->sg_lds[q] > SCAN_LDS_TWO_WG;
                 const int nt = one_wg ? SCAN_BLOCK_WIDE : SCAN_BLOCK;
-                if (split) {
-                    const int nt2 = one_wg ? SCAN_BLOCK_WIDE : SCAN2_BLOCK;
-                    (q == 0 ? k_scan2<true> : one_wg ? k_scan2<false, SCAN_BLOCK_WIDE> : k_scan2<false>)<<<
-                        (n_chunks + nt2 - 1) / nt2, nt2, e->sg_lds[q], sq>>>(
-                        Rq, g, text, reinterpret_cast<const uint32_t*>(e->bnd), e->lane_split, e->lane_perm, evq,
-                        cq, stq, e->d_err, scan_np);
-                } else {
-                    const uint32_t nb = (n_chunks + nt - 1) / nt;
-                    (q == 0 ? k_scan<true> : one_wg ? k_scan<false, SCAN_BLOCK_WIDE> : k_scan<false>)<<<
-                        nb, nt, e->sg_lds[q], sq>>>(Rq, g, text, e->bnd, e->lane_perm, evq, cq, stq, e->d_err,
-                                                    e->scan_ilv && nb <= e->n_cu ? nb : 0u, scan_np);
-                }
+                const uint32_t nb = (n_chunks + nt - 1) / nt;
+                (q == 0 ? k_scan<true> : one_wg ? k_scan<false, SCAN_BLOCK_WIDE> : k_scan<false>)<<<
+                    nb, nt, e->sg_lds[q], sq>>>(Rq, g, text, e->bnd, e->lane_perm, evq, cq, stq, e->d_err,
+                                                e->scan_ilv && nb <= e->n_cu ? nb : 0u, scan_np);
             }
             for (uint32_t i = 0; i + 1 < ns_scan; ++i) {
                 HIPCHK(hipEventRecord(e->ev_join[i], e->aux[i]));
@@ -6812,7 +6371,6 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
             hipMemcpy(e->d_sg_lds, lds32.data(), lds32.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
             return fail("hipMalloc failed");
     }
-    if (const char* v = std::getenv("PII_SCAN2")) e->scan2 = std::atoi(v) != 0;
     if (const char* v = std::getenv("PII_SCAN_COUNT")) e->scan_count = std::atoi(v) != 0;
     if (const char* v = std::getenv("PII_LONG_GATE")) e->long_gate = std::atoi(v) != 0;
     if (const char* v = std::getenv("PII_SCAN_ILV")) e->scan_ilv = std::atoi(v) != 0;
@@ -6820,21 +6378,12 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
     if (const char* v = std::getenv("PII_HALO_ITEMS")) e->halo_items = (uint32_t)std::max(0, std::min(HALO_ITEMS, std::atoi(v)));
     if (const char* v = std::getenv("PII_TIMING")) e->timing = std::max(0, std::min(2, std::atoi(v)));
     if (max_lds > 64 * 1024 &&
-        (hipFuncSetAttribute((const void*)k_scan2<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds) !=
-             hipSuccess ||
-         hipFuncSetAttribute((const void*)k_scan2<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds) !=
-             hipSuccess ||
-         hipFuncSetAttribute((const void*)k_scan2<false, SCAN_BLOCK_WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)max_lds) != hipSuccess))
-        return fail("cannot raise LDS limit");
-    if (max_lds > 64 * 1024 &&
         (hipFuncSetAttribute((const void*)k_scan<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds) !=
              hipSuccess ||
          hipFuncSetAttribute((const void*)k_scan<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds) !=
              hipSuccess ||
          hipFuncSetAttribute((const void*)k_scan<false, SCAN_BLOCK_WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)max_lds) != hipSuccess ||
-         hipFuncSetAttribute((const void*)k_halo, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds) != hipSuccess))
+                             (int)max_lds) != hipSuccess))
         return fail("cannot raise LDS limit");
     if (max_lds + FIX_LDS > 64 * 1024 &&
         hipFuncSetAttribute((const void*)k_scan_fix, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -6885,7 +6434,7 @@ int pii_engine_destroy(pii_engine* e) {
     if (!e) return PII_E_ARG;
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     void* ptrs[] = {e->d_rules, e->st_group, e->st_ts, e->stamp, e->ev, e->fd, e->n_ev, e->n_find,
-                    e->out_len, e->incl, e->agg_f, e->first_utt, e->lane_perm, e->lane_pos, e->lane_bkt, e->lane_cnt, e->bnd, e->lane_split, e->lane_spl, e->hist_part, e->evloc, e->lane_ev, e->pres, e->pend, e->lane_pair, e->lane_np, e->matched, e->mcount, e->cont,
+                    e->out_len, e->incl, e->agg_f, e->first_utt, e->lane_perm, e->lane_pos, e->lane_bkt, e->lane_cnt, e->bnd, e->hist_part, e->evloc, e->lane_ev, e->pres, e->pend, e->lane_pair, e->lane_np, e->matched, e->mcount, e->cont,
                     e->img_first.d, e->img_first_hot.d, e->img_eval.d, e->img_eval_rg.d, e->img_sel.d, e->img_sel_rg.d, e->kw, e->ctx, e->agg_v, e->commit,
                     e->span_offs, e->bsum, e->out_offs_tmp, e->lb_state, e->lb_ticket, e->d_err, e->d_totals, e->h_text, e->h_role,
                     e->h_out, e->h_offs, e->h_out_offs, e->h_slot, e->h_ts, e->h_spans, e->h_ctx,

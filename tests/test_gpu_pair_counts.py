@@ -1,4 +1,4 @@
-"""Pair counts at the source: the scan kernels (k_scan, k_scan2, and k_scan_fix's re-scan of a cut lane)
+"""Pair counts at the source: the scan kernels (k_scan, and k_scan_fix's re-scan of a cut lane)
 write each lane's (start, pattern) pair count next to its event count, the count pass
 k_pairs_flat<false> is not launched, and the write pass records the AGENT rows' keyword groups.
 PII_SCAN_COUNT=0 restores the count pass.  Nothing a caller sees may change: on the smallest shapes
