@@ -22,6 +22,7 @@ reported one step late, as a property of the state entered (see DESIGN.md §DFA 
 """
 from __future__ import annotations
 
+import base64
 import hashlib
 import io
 import json
@@ -795,13 +796,15 @@ def minimize(dfa: DFA) -> DFA:
 # What happens to a finding's bytes (dlp_config.yaml:195-199): per info type, the first transformation
 # that lists it, else the first without info_types, else the bytes stay (DLP leaves findings no
 # transformation names).  The values are the engine's PII_XF_* (include/pii_engine.h).
-XF_INFO_TYPE, XF_REPLACE, XF_REDACT, XF_MASK, XF_KEEP = range(5)
+XF_INFO_TYPE, XF_REPLACE, XF_REDACT, XF_MASK, XF_KEEP, XF_HASH = range(6)
 XF_MASK_WORDS = 8          # per type: char | reverse << 8, number_to_mask, 4 words of skip set, 2 spare
 XF_REPLACE_MAX = 255
+XF_HASH_LEN = 44           # base64 of a SHA-256 digest
+XF_HASH_KEY_WORDS = 16     # per key: the inner, then the outer HMAC midstate (8 words each)
 _XF_PRIMITIVES = {"replace_with_info_type_config": XF_INFO_TYPE, "replace_config": XF_REPLACE,
-                  "redact_config": XF_REDACT, "character_mask_config": XF_MASK}
+                  "redact_config": XF_REDACT, "character_mask_config": XF_MASK, "crypto_hash_config": XF_HASH}
 # every other primitive of DLP's PrimitiveTransformation: named in the error when one is configured
-_XF_UNSUPPORTED = ("crypto_replace_ffx_fpe_config", "crypto_hash_config", "crypto_deterministic_config",
+_XF_UNSUPPORTED = ("crypto_replace_ffx_fpe_config", "crypto_deterministic_config",
                    "date_shift_config", "bucketing_config", "fixed_size_bucketing_config", "time_part_config",
                    "replace_dictionary_config")
 _XF_COMMON = {"NUMERIC": "0123456789", "ALPHA_UPPER_CASE": "ABCDEFGHIJKLMNOPQRSTUVWXYZ",
@@ -817,6 +820,7 @@ class Transform:
     count: int = 0             # 0 = every character
     reverse: bool = False
     skip: int = 0              # 128-bit ASCII set: copied and not counted
+    key: bytes = b""           # XF_HASH: the HMAC-SHA256 key (32 or 64 bytes)
 
 
 def _parse_mask(cfg: dict) -> Transform:
@@ -851,6 +855,80 @@ def _parse_mask(cfg: dict) -> Transform:
     return Transform(XF_MASK, mask_char=ord(ch), count=n, reverse=rev, skip=skip)
 
 
+# crypto_hash_config: a finding becomes base64(HMAC-SHA256(key, finding bytes)).  The key fills at most
+# one 64-byte block, so HMAC's two keyed blocks (key ^ 0x36.., key ^ 0x5c..) can be compressed here, once:
+# the blob carries the two chaining values (midstates) per key and the engine continues from them.
+# hashlib does not expose a chaining value, hence the compression function below (FIPS 180-4, 6.2.2).
+_SHA256_K = (
+    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
+    0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
+    0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
+    0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
+    0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
+    0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
+    0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
+    0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2)
+SHA256_IV = (0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19)
+
+
+def sha256_compress(state: Sequence[int], block: bytes) -> Tuple[int, ...]:
+    """one SHA-256 compression: the chaining value after `block` (64 bytes) from chaining value `state`"""
+    assert len(block) == 64 and len(state) == 8
+    M = 0xFFFFFFFF
+
+    def rotr(x, n):
+        return ((x >> n) | (x << (32 - n))) & M
+    w = list(struct.unpack(">16I", block))
+    for i in range(16, 64):
+        s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3)
+        s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10)
+        w.append((w[i - 16] + s0 + w[i - 7] + s1) & M)
+    a, b, c, d, e, f, g, h = state
+    for i in range(64):
+        t1 = (h + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & M & g)) + _SHA256_K[i] + w[i]) & M
+        t2 = ((rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c))) & M
+        a, b, c, d, e, f, g, h = (t1 + t2) & M, a, b, c, (d + t1) & M, e, f, g
+    return tuple((x + y) & M for x, y in zip(state, (a, b, c, d, e, f, g, h)))
+
+
+def hmac_midstates(key: bytes) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """(inner, outer): the SHA-256 chaining values after key ^ 0x36.. and after key ^ 0x5c.. (key <= 64 bytes)"""
+    assert len(key) <= 64
+    k = key.ljust(64, b"\0")
+    return (sha256_compress(SHA256_IV, bytes(b ^ 0x36 for b in k)),
+            sha256_compress(SHA256_IV, bytes(b ^ 0x5C for b in k)))
+
+
+def _parse_hash(cfg: dict) -> Transform:
+    cfg = cfg or {}
+    unknown = set(cfg) - {"crypto_key"}
+    if unknown:
+        raise RuleError(f"crypto_hash_config: unsupported field {sorted(unknown)[0]}")
+    ck = cfg.get("crypto_key")
+    if not isinstance(ck, dict) or not ck:
+        raise RuleError("crypto_hash_config: crypto_key is missing")
+    for k in ck:
+        if k != "unwrapped":
+            known = "unsupported" if k in ("transient", "kms_wrapped") else "unknown"
+            raise RuleError(f"crypto_hash_config: {known} crypto_key form {k} (only unwrapped is supported)")
+    uw = ck["unwrapped"]
+    if not isinstance(uw, dict) or "key" not in uw:
+        raise RuleError("crypto_hash_config: crypto_key.unwrapped.key is missing")
+    unknown = set(uw) - {"key"}
+    if unknown:
+        raise RuleError(f"crypto_hash_config: unsupported field unwrapped.{sorted(unknown)[0]}")
+    b64 = uw["key"]
+    try:
+        if not isinstance(b64, str):
+            raise ValueError
+        key = base64.b64decode(b64, validate=True)
+    except ValueError:
+        raise RuleError("crypto_hash_config: crypto_key.unwrapped.key is not base64") from None
+    if len(key) not in (32, 64):
+        raise RuleError(f"crypto_hash_config: crypto_key.unwrapped.key is {len(key)} bytes (not 32 or 64)")
+    return Transform(XF_HASH, key=key)
+
+
 def _parse_primitive(prim: dict) -> Transform:
     prim = prim or {}
     if len(prim) != 1:
@@ -862,6 +940,8 @@ def _parse_primitive(prim: dict) -> Transform:
     kind = _XF_PRIMITIVES[name]
     if kind == XF_MASK:
         return _parse_mask(cfg)
+    if kind == XF_HASH:
+        return _parse_hash(cfg)
     if kind == XF_REPLACE:
         nv = (cfg or {}).get("new_value", {}) or {}
         if set(nv) != {"string_value"} or not isinstance(nv["string_value"], str):
@@ -921,6 +1001,8 @@ def transform_sections(transforms: Sequence[Transform]) -> "OrderedDict[str, np.
     for i, t in enumerate(transforms):
         if t.kind == XF_REPLACE:
             repl += t.value
+        if t.kind == XF_HASH:              # a placeholder of the surrogate's length; k_hash writes the bytes
+            repl += b"=" * XF_HASH_LEN
         off[i + 1] = len(repl)
         if t.kind == XF_MASK:
             mask[i, 0] = t.mask_char | (0x100 if t.reverse else 0)
@@ -931,6 +1013,16 @@ def transform_sections(transforms: Sequence[Transform]) -> "OrderedDict[str, np.
     out["xf.repl_off"] = off
     out["xf.repl"] = np.frombuffer(repl or b"\0", dtype=np.uint8).copy()
     out["xf.mask"] = mask.reshape(-1)
+    # crypto_hash_config (only with a hash type): per type a key index, per distinct key its two midstates.
+    # The midstates are as secret as the key: whoever holds them computes the same surrogates.
+    if any(t.kind == XF_HASH for t in transforms):
+        keys: List[bytes] = []
+        for t in transforms:
+            if t.kind == XF_HASH and t.key not in keys:
+                keys.append(t.key)
+        out["xf.hash_key"] = np.array([keys.index(t.key) if t.kind == XF_HASH else 0 for t in transforms],
+                                      dtype=np.uint32)
+        out["xf.hash_mid"] = np.array([w for k in keys for mid in hmac_midstates(k) for w in mid], dtype=np.uint32)
     return out
 
 

@@ -24,6 +24,7 @@
 //   k_redact       prefix-sum scatter of kept bytes and each finding's output (its "[INFO_TYPE]" token, or
 //                  what the rules' deidentify_config says for its type: out_len), span list, histogram
 //   k_mask         character_mask_config: masks the findings k_redact<true> copied (rules with a mask type)
+//   k_hash         crypto_hash_config: HMAC-SHA256 surrogates over k_redact's placeholders (rules with a hash type)
 //   k_ctx_commit   write the per-conversation context back (only when the call succeeded)
 #include <hip/hip_runtime.h>
 
@@ -111,7 +112,8 @@ struct RulesDev {
     const uint32_t* excl_off;    // [V*T+1]
     const uint16_t* excl_ids;
     const uint32_t* tok_off;     // [T+1] into tok_bytes: a type's fixed output ("[NAME]", its replace_config
-                                 // string, nothing for redact_config / mask / keep)
+                                 // string, a hash type's 44-byte placeholder, nothing for redact_config / mask /
+                                 // keep)
     const uint8_t* tok_bytes;
     const uint32_t* tok_len;     // [T+1] per type: its fixed output length, or XF_SAME_LEN (mask / keep); see out_len
     const uint8_t* xf_kind;      // [T] PII_XF_*
@@ -124,6 +126,8 @@ struct RulesDev {
 // for a type no transformation names.  `tl` is the per-type table (RulesDev::tok_len or its LDS copy).
 constexpr uint32_t XF_SAME_LEN = 0x80000000u;
 constexpr int XF_MASK_WORDS = 8;
+constexpr int XF_HASH_KEY_WORDS = 16;
+constexpr uint32_t XF_HASH_LEN = 44;      // base64 of a SHA-256 digest
 __device__ __forceinline__ uint32_t out_len(const uint32_t* tl, uint32_t t, uint32_t in_len) {
     const uint32_t l = tl[t];
     return (l & XF_SAME_LEN) ? in_len : l;
@@ -3639,6 +3643,152 @@ __global__ __launch_bounds__(256) void k_mask(const RulesDev R, const uint8_t* _
     }
 }
 
+// ------------------------------------------------------------------------ crypto_hash_config (k_hash)
+// SHA-256 (FIPS 180-4) on the vector ALUs.  One compression keeps the message schedule as a rolling
+// 16-word window and unrolls the 64 rounds, so every array index is a compile-time constant and the
+// state, the window and the round constants (literals) stay in registers: no scratch.
+__device__ __forceinline__ uint32_t sha_rotr(uint32_t x, int n) { return __builtin_amdgcn_alignbit(x, x, n); }
+
+__device__ __forceinline__ void sha256_compress(uint32_t (&h)[8], uint32_t (&w)[16]) {
+    constexpr uint32_t K[64] = {
+        0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
+        0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
+        0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
+        0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
+        0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
+        0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
+        0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
+        0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+    uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
+#pragma unroll
+    for (int i = 0; i < 64; ++i) {
+        if (i >= 16) {
+            const uint32_t w15 = w[(i + 1) & 15], w2 = w[(i + 14) & 15];
+            w[i & 15] += (sha_rotr(w15, 7) ^ sha_rotr(w15, 18) ^ (w15 >> 3)) + w[(i + 9) & 15] +
+                         (sha_rotr(w2, 17) ^ sha_rotr(w2, 19) ^ (w2 >> 10));
+        }
+        const uint32_t t1 = hh + (sha_rotr(e, 6) ^ sha_rotr(e, 11) ^ sha_rotr(e, 25)) + (g ^ (e & (f ^ g))) + K[i] +
+                            w[i & 15];
+        const uint32_t t2 = (sha_rotr(a, 2) ^ sha_rotr(a, 13) ^ sha_rotr(a, 22)) + ((a & b) | (c & (a | b)));
+        hh = g;
+        g = f;
+        f = e;
+        e = d + t1;
+        d = c;
+        c = b;
+        b = a;
+        a = t1 + t2;
+    }
+    h[0] += a;
+    h[1] += b;
+    h[2] += c;
+    h[3] += d;
+    h[4] += e;
+    h[5] += f;
+    h[6] += g;
+    h[7] += hh;
+}
+
+// character c (0..42) of the base64 of the 256-bit digest d[0..7] (d[8] = 0: the last character's low bits)
+template <int C>
+__device__ __forceinline__ uint8_t b64_char(const uint32_t (&d)[9]) {
+    constexpr int p = 6 * C, wi = p >> 5, o = p & 31;
+    uint32_t v;
+    if constexpr (o <= 26) v = d[wi] >> (26 - o);
+    else v = (d[wi] << (o - 26)) | (d[wi + 1] >> (58 - o));
+    v &= 63u;
+    uint32_t ch = v + 65u;                  // A-Z
+    ch += v >= 26u ? 6u : 0u;               // a-z
+    ch -= v >= 52u ? 75u : 0u;              // 0-9
+    ch -= v >= 62u ? 15u : 0u;              // +
+    ch += v == 63u ? 3u : 0u;               // /
+    return (uint8_t)ch;
+}
+template <int C>
+__device__ __forceinline__ void b64_store(const uint32_t (&d)[9], uint8_t* o) {
+    if constexpr (C < 43) {
+        o[C] = b64_char<C>(d);
+        b64_store<C + 1>(d, o);
+    }
+}
+
+// crypto_hash_config, after k_redact has copied a hash type's 44-byte placeholder: one thread per span
+// computes base64(HMAC-SHA256(key, finding bytes)) and writes it over the placeholder.  The rules carry
+// the key as its two midstates (the SHA-256 state after the key ^ ipad and the key ^ opad block), so the
+// inner hash continues from the first over the finding's bytes (total length 64 + len) and the outer
+// from the second over the 32-byte inner digest (total length 96): ceil((len + 9) / 64) + 1 compressions.
+// The text is read as 16-byte windows (load16: only aligned chunks that hold a byte of the span).  The
+// output length never depends on the text (out_len), so exactly the span's own 44 output bytes are
+// written.  Launched only for rules with a hash type; its two tables (hash_key: per type a key index,
+// hash_mid: per key XF_HASH_KEY_WORDS words) are its own arguments, RulesDev does not carry them.
+constexpr int HASH_BLOCK = 256;
+__global__ __launch_bounds__(HASH_BLOCK) void k_hash(const uint8_t* __restrict__ xf_kind,
+                                                     const uint32_t* __restrict__ hash_key,
+                                                     const uint32_t* __restrict__ hash_mid,
+                                                     const uint8_t* __restrict__ text,
+                                                     const uint64_t* __restrict__ offs,
+                                                     const RSpan* __restrict__ rsp,
+                                                     const uint64_t* __restrict__ n_spans_p,
+                                                     const uint32_t* __restrict__ err, uint8_t* __restrict__ out) {
+    if (*err != 0) return;
+    const uint64_t si = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;      // span index
+    if (si >= *n_spans_p) return;
+    const RSpan r = rsp[si];
+    const uint32_t t = rs_type(r);
+    if (xf_kind[t] != PII_XF_HASH) return;
+    const uint32_t* mid = hash_mid + (size_t)hash_key[t] * XF_HASH_KEY_WORDS;
+    const uint8_t* in = text + offs[0] + r.in_lo;
+    const int len = (int)(r.in_hi - r.in_lo);
+    uint32_t h[8], w[16];
+    {
+        const uint4 m0 = *reinterpret_cast<const uint4*>(mid), m1 = *reinterpret_cast<const uint4*>(mid + 4);
+        h[0] = m0.x, h[1] = m0.y, h[2] = m0.z, h[3] = m0.w, h[4] = m1.x, h[5] = m1.y, h[6] = m1.z, h[7] = m1.w;
+    }
+    // inner hash: the data blocks, 0x80 after the last byte, zeros, and the bit length in the last two
+    // words of the first block with room for it (rem <= 55, rem = bytes left at the block's start; < 0 in
+    // a block that holds only padding)
+    for (int base = 0;; base += 64) {
+        const int rem = len - base;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int n = rem - 16 * q;                    // span bytes from this window's start
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (n > 0) v = load16(in + base + 16 * q, 0, n < 16 ? n : 16);
+            const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int m = n - 4 * k;                   // ... from this word's start
+                uint32_t u = x[k] & bytemask(m);
+                if (m >= 0 && m < 4) u |= 0x80u << (8 * m);
+                w[4 * q + k] = __builtin_bswap32(u);
+            }
+        }
+        const bool last = rem <= 55;
+        if (last) {
+            w[14] = 0;                                     // (len < 2^29: the length fits the low word)
+            w[15] = (64u + (uint32_t)len) * 8u;
+        }
+        sha256_compress(h, w);
+        if (last) break;
+    }
+    // outer hash: the inner digest, padded to one block, total length 64 + 32 bytes
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = h[i];
+    w[8] = 0x80000000u;
+#pragma unroll
+    for (int i = 9; i < 15; ++i) w[i] = 0;
+    w[15] = 96u * 8u;
+    {
+        const uint4 m0 = *reinterpret_cast<const uint4*>(mid + 8), m1 = *reinterpret_cast<const uint4*>(mid + 12);
+        h[0] = m0.x, h[1] = m0.y, h[2] = m0.z, h[3] = m0.w, h[4] = m1.x, h[5] = m1.y, h[6] = m1.z, h[7] = m1.w;
+    }
+    sha256_compress(h, w);
+    const uint32_t d[9] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], 0u};
+    uint8_t* o = out + rs_out(r);
+    b64_store<0>(d, o);
+    o[43] = '=';
+}
+
 // per-info-type totals of the redact tiles' histograms (one atomic per type, no same-address storms)
 __global__ __launch_bounds__(256) void k_hist_reduce(const uint32_t* __restrict__ hist_part, uint32_t n_tiles, int T,
                                                      const uint32_t* __restrict__ err,
@@ -4813,9 +4963,11 @@ struct pii_engine {
     uint32_t first_p_hot = 0;
     bool lists_cl = false;
     // deidentify_config (optional xf.* blob sections): per-type PII_XF_*; any mask / keep type (k_redact<true>,
-    // the FULL window re-scan), any mask type (k_mask)
+    // the FULL window re-scan), any mask type (k_mask), any hash type (k_hash, the FULL window re-scan)
     std::vector<uint8_t> xf_kind;
-    bool xf_src = false, xf_mask = false;
+    bool xf_src = false, xf_mask = false, xf_hash = false;
+    const uint32_t* d_hash_key = nullptr;    // (in d_rules) per type: key index; per key: its two HMAC midstates
+    const uint32_t* d_hash_mid = nullptr;
     hipStream_t aux[2] = {nullptr, nullptr};   // more streams for the SCAN groups' passes (PII_SCAN_STREAMS)
     uint32_t n_aux = 0;
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};             // the images' rule / exclusion lists are deduplicated (list_range)
@@ -5504,6 +5656,11 @@ int run_pipeline(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                 k_mask<<<(uint32_t)(ms / 256) + 1, 256, 0, st>>>(R, text, offs, e->rsp, e->lane_sp + n_chunks, e->d_err,
                                                                  out);
             }
+            if (e->xf_hash) {   // (the same bound on the span count)
+                const uint64_t ms = std::min<uint64_t>(span_cap, total_bytes / (uint64_t)Rsel.min_len + n_chunks);
+                k_hash<<<(uint32_t)(ms / HASH_BLOCK) + 1, HASH_BLOCK, 0, st>>>(
+                    R.xf_kind, e->d_hash_key, e->d_hash_mid, text, offs, e->rsp, e->lane_sp + n_chunks, e->d_err, out);
+            }
             if (e->timing >= 1) HIPCHK(hipEventRecord(e->kev[3], st));
             if (!wf)        // (window findings are not counted, as on the incremental window path)
                 k_hist_reduce<<<dim3(e->hist_types, std::max(1u, std::min(32u, nsb / 256))), 256, 0, st>>>(
@@ -5956,6 +6113,8 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
     std::vector<uint32_t> xf_maskp((size_t)std::max(R.T, 1) * XF_MASK_WORDS, 0u);
     const Section* xs_repl_off = nullptr;
     const Section* xs_repl = nullptr;
+    const Section* xs_hkey = nullptr;
+    const Section* xs_hmid = nullptr;
     if (const Section* xk = find("xf.kind")) {
         xs_repl_off = find("xf.repl_off");
         xs_repl = find("xf.repl");
@@ -5965,11 +6124,24 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
             return fail("transformation tables malformed");
         const uint32_t* ro = reinterpret_cast<const uint32_t*>(xs_repl_off->data);
         for (int t = 0; t < R.T; ++t) {
-            if (xk->data[t] > PII_XF_KEEP || ro[t] > ro[t + 1] || ro[t + 1] > xs_repl->bytes || ro[t + 1] - ro[t] > 255)
+            if (xk->data[t] > PII_XF_HASH || ro[t] > ro[t + 1] || ro[t + 1] > xs_repl->bytes || ro[t + 1] - ro[t] > 255)
                 return fail("transformation tables malformed");
             e->xf_kind[t] = xk->data[t];
             e->xf_src |= xk->data[t] == PII_XF_MASK || xk->data[t] == PII_XF_KEEP;
             e->xf_mask |= xk->data[t] == PII_XF_MASK;
+            e->xf_hash |= xk->data[t] == PII_XF_HASH;
+        }
+        if (e->xf_hash) {   // per type a key index, per key two midstates; a hash type's replacement is its placeholder
+            xs_hkey = find("xf.hash_key");
+            xs_hmid = find("xf.hash_mid");
+            if (!xs_hkey || !xs_hmid || xs_hkey->bytes != (size_t)R.T * 4 || xs_hmid->bytes == 0 ||
+                xs_hmid->bytes % (XF_HASH_KEY_WORDS * 4) != 0)
+                return fail("transformation tables malformed");
+            const uint32_t* hk = reinterpret_cast<const uint32_t*>(xs_hkey->data);
+            for (int t = 0; t < R.T; ++t)
+                if (e->xf_kind[t] == PII_XF_HASH &&
+                    (hk[t] >= xs_hmid->bytes / (XF_HASH_KEY_WORDS * 4) || ro[t + 1] - ro[t] != XF_HASH_LEN))
+                    return fail("transformation tables malformed");
         }
         std::memcpy(xf_maskp.data(), xm->data, xm->bytes);
         for (int t = 0; t < R.T; ++t)
@@ -5983,12 +6155,13 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
     for (int t = 0; t < R.T; ++t) {
         if (e->xf_kind[t] == PII_XF_INFO_TYPE) {
             tok += "[" + e->names[t] + "]";
-        } else if (e->xf_kind[t] == PII_XF_REPLACE) {
+        } else if (e->xf_kind[t] == PII_XF_REPLACE || e->xf_kind[t] == PII_XF_HASH) {   // (hash: the placeholder)
             const uint32_t* ro = reinterpret_cast<const uint32_t*>(xs_repl_off->data);
             tok.append(reinterpret_cast<const char*>(xs_repl->data) + ro[t], ro[t + 1] - ro[t]);
         }
         tok_off[t + 1] = (uint32_t)tok.size();
-        tok_len[t] = e->xf_kind[t] >= PII_XF_MASK ? XF_SAME_LEN : tok_off[t + 1] - tok_off[t];
+        const bool same_len = e->xf_kind[t] == PII_XF_MASK || e->xf_kind[t] == PII_XF_KEEP;
+        tok_len[t] = same_len ? XF_SAME_LEN : tok_off[t + 1] - tok_off[t];
     }
     tok += "\n";               // the re-scan window separator (k_win_redact piece source)
     R.nl_off = (uint32_t)tok.size() - 1;
@@ -6088,6 +6261,11 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
         gp.push_back({add(h.cmap4.data(), 1024), add(h.td.data(), h.td.size() * 2), add(h.tk.data(), 4),
                       add(h.dacc.data(), h.dacc.size() * 2), add(h.kacc.data(), 4),
                       add(h.npair.data(), h.npair.size() * 2)});
+    size_t i_hk = 0, i_hm = 0;      // (after every other table: rules without a hash type keep their layout)
+    if (e->xf_hash) {
+        i_hk = add(xs_hkey->data, xs_hkey->bytes);
+        i_hm = add(xs_hmid->data, xs_hmid->bytes);
+    }
     if (hipSetDevice(device) != hipSuccess) { e->err = "hipSetDevice failed"; pii_engine_destroy(e); return PII_E_DEVICE; }
     if (hipMalloc(&e->d_rules, total) != hipSuccess) return fail("hipMalloc rules failed");
     std::vector<uint8_t> host(total, 0);
@@ -6124,6 +6302,10 @@ int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_sl
     R.tok_len = (const uint32_t*)at(i_tl);
     R.xf_kind = (const uint8_t*)at(i_xk);
     R.xf_mask = (const uint32_t*)at(i_xm);
+    if (e->xf_hash) {
+        e->d_hash_key = (const uint32_t*)at(i_hk);
+        e->d_hash_mid = (const uint32_t*)at(i_hm);
+    }
     if (R.n_dacc >= 65535) return fail("too many SCAN accept sets");
     {   // per-kernel LDS images
         auto sec = [&](const char* nm) { return std::make_pair((const void*)find(nm)->data, (size_t)find(nm)->bytes); };
@@ -6872,9 +7054,9 @@ int pii_window_enable_ex(pii_engine* e, uint32_t window_n, uint32_t slot_bytes, 
     // (config 5: the groups' merged pair queue, candidate lists past LIVE patterns spilled like
     // k_select's) and tables past LDS (read in place); any other rule set re-scans the joined windows
     // in full
-    // (a mask / keep type's output comes from the text: the window redaction kernel's pieces do not
-    // produce it, the scan+redact pipeline the full re-scan runs does)
-    e->win_full = (flags & PII_WINDOW_FULL) || !e->window_ok || e->xf_src;
+    // (a mask / keep type's output comes from the text, a hash type's is computed from it: the window
+    // redaction kernel's pieces do not produce either, the scan+redact pipeline the full re-scan runs does)
+    e->win_full = (flags & PII_WINDOW_FULL) || !e->window_ok || e->xf_src || e->xf_hash;
     e->win_n = window_n;
     e->win_slot_bytes = slot_bytes;
     return PII_OK;

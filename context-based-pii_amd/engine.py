@@ -31,7 +31,7 @@ EXPORTS = ["pii_engine_create", "pii_engine_destroy", "pii_engine_info", "pii_ty
            "pii_context_update", "pii_set_timing", "pii_type_transform"]
 PII_WINDOW_FULL = 1
 # pii_type_transform: what the rules' deidentify_config does with a finding of a type
-PII_XF_INFO_TYPE, PII_XF_REPLACE, PII_XF_REDACT, PII_XF_MASK, PII_XF_KEEP = range(5)
+PII_XF_INFO_TYPE, PII_XF_REPLACE, PII_XF_REDACT, PII_XF_MASK, PII_XF_KEEP, PII_XF_HASH = range(6)
 
 
 class PiiError(RuntimeError):

@@ -86,12 +86,16 @@ int pii_type_name(struct pii_engine* e, uint32_t t, char* buf, size_t cap);
  *   REPLACE    replace_config: the configured string (0..255 bytes)
  *   REDACT     redact_config: the finding is removed
  *   MASK       character_mask_config: same byte length, every byte of a masked code point replaced
- *   KEEP       no transformation applies: the bytes stay (the finding is still reported) */
+ *   KEEP       no transformation applies: the bytes stay (the finding is still reported)
+ *   HASH       crypto_hash_config: base64(HMAC-SHA256(key, finding bytes)), always 44 bytes.  The blob
+ *              holds, per key, the two HMAC midstates (xf.hash_mid) instead of the key; they are as
+ *              secret as the key */
 #define PII_XF_INFO_TYPE 0
 #define PII_XF_REPLACE 1
 #define PII_XF_REDACT 2
 #define PII_XF_MASK 3
 #define PII_XF_KEEP 4
+#define PII_XF_HASH 5
 int pii_type_transform(struct pii_engine* e, uint32_t t);
 /* name of the context group `g` (its expected_pii_type) */
 int pii_context_group_type(struct pii_engine* e, uint32_t g);
@@ -246,7 +250,8 @@ int pii_last_stats(struct pii_engine* e, uint64_t* out, uint32_t n);
  * and SCAN groups, tables in LDS or read in place); otherwise (a '\n'-consuming detector) by a FULL
  * re-scan -- the ring then keeps the raw text, every row's "\n"-joined window is materialised in HBM
  * and run through the scan+redact pipeline (one host wait per call for the joined size).  Rules with a
- * PII_XF_MASK or PII_XF_KEEP type (output bytes taken from the text) also take the FULL re-scan. */
+ * PII_XF_MASK, PII_XF_KEEP or PII_XF_HASH type (output bytes taken or computed from the text) also
+ * take the FULL re-scan. */
 #define PII_WINDOW_MAX 8
 #define PII_WINDOW_FULL 1   /* pii_window_enable_ex flag / pii_window_mode result: full re-scan */
 /* allocate the per-slot window history (n_conv_slots * slot_bytes of HBM); window_n <= PII_WINDOW_MAX,
