@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pii_layout.h"
+
 namespace pii {
 
 // character kinds used by the DFA start states (compiler.K_BOT/K_W/K_N)
@@ -331,7 +333,6 @@ __device__ inline bool validate(int id, const uint8_t* q, int n) {
 // In the kernels' LDS images every transition entry is  next_state | flags(next_state) << 14
 // (FIRST: bit 14 = a match ended before the byte just consumed, bit 15 = terminal; HOT: bit 14 =
 // accept), so one step is two dependent LDS reads (byte class, transition).
-constexpr uint32_t DFA_STATE_MASK = 0x3fffu;
 struct Pool {
     const uint16_t* trans;
     const uint8_t* cmap;

@@ -31,7 +31,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <map>
 #include <cstring>
 #include <string>
 #include <unordered_map>
@@ -39,12 +38,12 @@
 
 #include "../../include/pii_engine.h"
 #include "pii_device.h"
+#include "pii_rules_host.h"
 
 using namespace pii;
 
 namespace {
 
-constexpr int NE_MAX = 2;          // excluder patterns
 constexpr size_t SCAN_LDS_TWO_WG = 80 * 1024;   // k_scan tables up to this: two workgroups per CU
 #ifndef SCAN1_BLOCK
 #define SCAN1_BLOCK 768
@@ -61,7 +60,6 @@ constexpr int SCAN_TILE = 256 * SCAN_ITEMS;
 #endif
 constexpr uint32_t BYTES_PER_LANE = BYTES_PER_LANE_N;    // largest scan lane (big batches)
 constexpr uint32_t MIN_LANE_SHIFT = 7;        // smallest scan lane, 128 B (small batches need lanes, not bytes)
-constexpr int KW_NONE = 0x7fff;
 constexpr int PAIRS_UCAP = 1024;   // utterances a wavefront stages in LDS (k_pairs_flat)
 
 enum : uint32_t { ERR_CAPACITY = 1, ERR_ORDER = 2, ERR_SLOT = 4, ERR_QUEUE = 8, ERR_RING = 16, ERR_STITCH = 32,
@@ -78,56 +76,9 @@ struct Event {
     uint16_t sk;    // K transition index (row + class)
 };
 
-struct RulesDev {
-    int P, G, T, V, SD, CD, d_start, SK, CK, k_start, n_hot, min_len;
-    int kw_always_min, NE;
-    int CDs, CKs;                // row strides of the SCAN tables (CD / CK rounded up to even; a WIDE
-                                 // group's D: to a multiple of 4)
-    int dsh;                     // D entry = row byte offset >> dsh (| flags): 0, or 1 for a WIDE SCAN
-                                 // group >= 1 (D table up to 128 KiB; its class words carry no K half)
-    uint32_t n_dacc, n_kacc;     // D / K accept sets
-    const uint32_t* cmap4;    // [256] 2*classD | 2*classK << 16 (byte offsets)
-    const uint16_t* td;       // [SD*CDs] LDS byte address of the next row in k_scan | accept (bit 0)
-                              //   | the next row's end-of-text transition accepts (bit 1)
-    const uint16_t* tk;       // [SK*CKs]
-    const uint16_t* d_accid;  // [SD*CDs]
-    const uint32_t* d_na;     // [SD*CDs] d_npair | d_accid << 16 (the pair write pass: one gather for both)
-    const uint32_t* d_acc_off;
-    const uint16_t* d_acc_ids;
-    const uint16_t* k_accid;  // [SK*CKs]
-    const uint16_t* k_acc_min;  // per K accept set: smallest context group
-    const uint16_t* d_npair;    // [SD*CDs] per D transition: pairs of its accept set (k_pairs count pass)
-    const uint16_t* k_grp;      // [SK*CKs] per K transition: smallest context group it accepts, or KW_NONE
-    const uint16_t* det_type;
-    const uint8_t* det_val;
-    const uint8_t* det_lik;
-    const uint8_t* det_exidx;   // excluder slot or 0xff
-    const int32_t* first_desc;  // [P*8]
-    const int32_t* hot_rule;    // [n_hot*4] wb, wa, fixed, rel
-    const int32_t* hot_desc;    // [n_hot*8]
-    const uint8_t* var_enabled;  // [V*T]
-    const uint8_t* var_minlik;   // [V]
-    const uint32_t* rule_off;    // [V*T+1]
-    const uint16_t* rule_ids;
-    const uint32_t* excl_off;    // [V*T+1]
-    const uint16_t* excl_ids;
-    const uint32_t* tok_off;     // [T+1] into tok_bytes: a type's fixed output ("[NAME]", its replace_config
-                                 // string, a hash type's 44-byte placeholder, nothing for redact_config / mask /
-                                 // keep)
-    const uint8_t* tok_bytes;
-    const uint32_t* tok_len;     // [T+1] per type: its fixed output length, or XF_SAME_LEN (mask / keep); see out_len
-    const uint8_t* xf_kind;      // [T] PII_XF_*
-    const uint32_t* xf_mask;     // [T*XF_MASK_WORDS] mask types: char | reverse << 8, number_to_mask, 128-bit skip set
-    uint32_t nl_off;             // tok_bytes[nl_off] = '\n' (the re-scan window separator)
-};
-
 // Output length of a finding of type t over in_len input bytes (deidentify_config): the token or
 // replacement length of the fixed kinds (0 for redact_config), in_len for character_mask_config and
 // for a type no transformation names.  `tl` is the per-type table (RulesDev::tok_len or its LDS copy).
-constexpr uint32_t XF_SAME_LEN = 0x80000000u;
-constexpr int XF_MASK_WORDS = 8;
-constexpr int XF_HASH_KEY_WORDS = 16;
-constexpr uint32_t XF_HASH_LEN = 44;      // base64 of a SHA-256 digest
 __device__ __forceinline__ uint32_t out_len(const uint32_t* tl, uint32_t t, uint32_t in_len) {
     const uint32_t l = tl[t];
     return (l & XF_SAME_LEN) ? in_len : l;
@@ -462,10 +413,6 @@ __global__ __launch_bounds__(256) void k_lane_place(const Geo g, uint32_t* __res
     }
 }
 
-// table entries are absolute LDS byte addresses of the next row, bit 0 = accept (scan_tables); k_scan
-// has no static LDS, so its dynamic region starts at LDS address 0 and an entry IS the address
-constexpr uint32_t SCAN_TD_BASE = 1024;     // after the 256-entry class map
-constexpr uint32_t SCAN_SPREAD_BYTES = 512; // k_scan's 256 group masks (scan_spread), after the K table
 typedef const __attribute__((address_space(3))) uint16_t lds_u16_t;
 __device__ __forceinline__ uint32_t lds_u16(uint32_t addr) {
     return *reinterpret_cast<lds_u16_t*>((size_t)addr);
@@ -898,10 +845,6 @@ __device__ void rescan_lane(const RulesDev& R, const Geo& g, const uint8_t* __re
     if (L.clo) lane_st[2 * c + 1] = scan_state(nd, nk);
 }
 
-constexpr int FIX_Q = 512;
-// LDS past the scan tables (the tables' entries are absolute LDS addresses, so the kernel declares no
-// static LDS): queue, entry states, previous round's lanes, counters
-constexpr size_t FIX_LDS = (3 * FIX_Q + 4) * 4;
 #ifndef SCAN_STREAMS
 #define SCAN_STREAMS 3                // streams for several SCAN groups' passes (config 5, wall per step, one box:
                                       // 1 / 2 / 3 -> 6.65 / 6.31 / 6.28 ms)
@@ -1306,14 +1249,6 @@ struct PairRes {       // one (start, pattern) candidate (8 B); its FIRST end li
     int16_t lik;       // likelihood after validation + hotwords; -1 = invalid
 };
 
-// LDS images of rule tables, one per kernel (only what that kernel reads, so the pair kernels keep
-// two 1024-thread workgroups per CU).  Sections are 16-byte aligned; off[] are byte offsets.
-constexpr int IMG_MAX = 16;
-struct LdsImage {
-    uint32_t off[IMG_MAX];
-    uint32_t total;    // bytes, multiple of 16
-    uint32_t aux;      // index widths of the image's list tables (list_range): rule lists | exclusion lists << 3
-};
 // Per-(variant, type) hotword-rule and exclusion lists, deduplicated: key i -> list L = ix[i] (an index
 // `w` bytes wide; w = 0: L = i, the undeduplicated global tables) -> ids[loff[L], loff[L + 1]).  Config 5
 // has 23349 keys but 29 distinct rule lists and 2 exclusion lists: one byte per key instead of four,
@@ -1332,12 +1267,6 @@ __device__ __forceinline__ void list_range(const void* ix, uint32_t w, const uin
     r0 = loff[L];
     r1 = loff[L + 1];
 }
-enum { FI_TRANS, FI_CMAP, FI_DESC, FI_N };
-enum { EV_TRANS, EV_CMAP, EV_HDESC, EV_HRULE, EV_DTYPE, EV_DVAL, EV_DLIK, EV_ROFF, EV_RIDS, EV_THOT, EV_RLOFF, EV_N };
-// k_win_select: everything k_select reads + the HOT automata and the variants' hotword rule lists
-enum { WS_TRANS, WS_CMAP, WS_HDESC, WS_HRULE, WS_DTYPE, WS_DLIK, WS_VEN, WS_VMIN, WS_DEX, WS_XOFF, WS_XIDS,
-       WS_TOKOFF, WS_ROFF, WS_RIDS, WS_RLOFF, WS_XLOFF, WS_N };
-enum { SE_DTYPE, SE_VEN, SE_VMIN, SE_DEX, SE_XOFF, SE_XIDS, SE_TOKOFF, SE_XLOFF, SE_N };
 
 constexpr int PAIR_BLOCK = 1024;
 
@@ -1385,7 +1314,6 @@ constexpr int PAIRS_BLOCK = 256;
 // excluders) comes first among one start's pairs, and writes the pairs.  (A per-lane walk
 // of the merge -- one thread per lane, two dependent global loads per event -- took 1026 us at config
 // 5; the rank form below 597 us.)
-constexpr int SCAN_GROUPS_MAX = 8;
 struct AccTabs {                 // per SCAN group, by D transition index:
     const uint16_t* accid[SCAN_GROUPS_MAX];   // global D accept-set id
     const uint16_t* npair[SCAN_GROUPS_MAX];   // pairs of that accept set
@@ -4794,83 +4722,10 @@ __global__ __launch_bounds__(256) void k_begin(uint32_t* __restrict__ d_err, con
 
 __global__ void k_noop() {}
 
-// ------------------------------------------------------------------------------- LDS images
-// DFAs re-packed into a kernel's own pool (descriptor offsets rebased; each transition entry carries
-// the destination's flags in bits 14-15, see pii_device.h)
-struct DfaPool {
-    std::vector<uint16_t> trans;
-    std::vector<uint8_t> cmap;
-    std::vector<int32_t> desc;
-};
-// pre: a FIRST automaton's PRE state (absorbed match starts, first_begin), -1 = none
-bool add_dfa(DfaPool& dp, const int32_t* d, const uint16_t* trans, const uint8_t* flags, const uint8_t* cmap,
-             int32_t pre = -1) {
-    const int32_t nc = d[3], ns = d[7];
-    if (ns > (int32_t)DFA_STATE_MASK + 1) return false;
-    int32_t nd[8];
-    std::memcpy(nd, d, sizeof(nd));
-    // LDS bank stagger (32 banks x 4 B): a pair kernel's wavefront runs many patterns' automata over
-    // the same text bytes, so automaton k's transition table starts at bank k mod 32 and its class map
-    // 4 bytes after the previous map's end (byte c of every map would otherwise sit in one bank)
-    const size_t k = dp.desc.size() / 8;
-    while (dp.trans.size() % 64 != (2 * k) % 64) dp.trans.push_back(0);
-    nd[0] = (int32_t)dp.trans.size();
-    nd[1] = pre < 0 ? 0 : pre + 1;
-    nd[2] = (int32_t)dp.cmap.size();
-    for (size_t i = 0; i < (size_t)ns * nc; ++i) {
-        const uint16_t dst = trans[d[0] + i];
-        dp.trans.push_back((uint16_t)(dst | ((flags[d[1] + dst] & 3u) << 14)));
-    }
-    dp.cmap.insert(dp.cmap.end(), cmap + d[2], cmap + d[2] + 256);
-    dp.cmap.insert(dp.cmap.end(), 4, (uint8_t)0);
-    dp.desc.insert(dp.desc.end(), nd, nd + 8);
-    return true;
-}
-
-// ------------------------------------------------------------------------------- blob parsing
-struct Section {
-    std::string name;
-    uint32_t dtype;
-    const uint8_t* data;
-    uint64_t bytes;
-};
-
-bool parse_blob(const uint8_t* p, size_t n, std::vector<Section>& out) {
-    if (n < 12 || std::memcmp(p, "PIIRULE1", 8) != 0) return false;
-    uint32_t cnt;
-    std::memcpy(&cnt, p + 8, 4);
-    size_t off = 12;
-    for (uint32_t i = 0; i < cnt; ++i) {
-        uint32_t ln;
-        if (off + 4 > n) return false;
-        std::memcpy(&ln, p + off, 4);
-        off += 4;
-        if (off + ln + 12 > n) return false;
-        Section s;
-        s.name.assign(reinterpret_cast<const char*>(p + off), ln);
-        off += ln;
-        std::memcpy(&s.dtype, p + off, 4);
-        std::memcpy(&s.bytes, p + off + 4, 8);
-        off += 12;
-        if (off + s.bytes > n) return false;
-        s.data = p + off;
-        off += s.bytes;
-        off += (8 - off % 8) % 8;
-        out.push_back(s);
-    }
-    return true;
-}
-
 }  // namespace
 
 // ================================================================================ engine object
-constexpr size_t IMG_LDS_MAX = 160 * 1024;
-// k_pair_first<true>'s LDS copy: most of the LDS, one 1024-thread workgroup per CU (config 5: 40 / 78 /
-// 156 KB -> 999 / 934 / 885 us: more automata in LDS beat two workgroups per CU)
-constexpr size_t FIRST_HOT_LDS = 156 * 1024;
-constexpr size_t FIRST_HOT_BIG = 8 * 1024;      // ... which skips automata larger than this (prefix of
-                                                // ids, 78 KB: 982 -> 933 us)
-constexpr size_t IMG_LDS_SPLIT = 80 * 1024;    // pair-kernel image size past which its per-(variant, type) lists stay in L2
+// one kernel's image in device memory (its host form: HostImage, pii_rules_host.h)
 struct DevImage {
     LdsImage li{};
     uint4* d = nullptr;
@@ -4878,67 +4733,33 @@ struct DevImage {
     size_t lds() const { return global ? 0 : li.total; }
 };
 
-// a per-(variant, type) list table, deduplicated for the LDS images (list_range)
-struct ListTab {
-    std::vector<uint8_t> ix;      // per key: list number, w bytes
-    std::vector<uint32_t> loff;   // per list: first id, + end
-    std::vector<uint16_t> ids;
-    uint32_t w = 1;
+// the window history rings (pii_window_enable, pii_context_resize): persistent per-slot state, plain
+// allocations outside the work-buffer accounting
+struct WinTables {
+    WDesc* desc = nullptr;
+    uint32_t *cnt = nullptr, *head = nullptr;
+    uint8_t* arena = nullptr;
 };
-// (a small table stays as it is -- w = 0, ix empty: one LDS read less per lookup; config 2's list
-// lookups in k_select cost 4 us more through the index)
-constexpr size_t LIST_DEDUP_KEYS = 8192;
-static ListTab dedup_lists(const uint32_t* off, const uint16_t* ids, size_t n_keys) {
-    ListTab t;
-    if (n_keys <= LIST_DEDUP_KEYS) {
-        t.w = 0;
-        t.ix.push_back(0);
-        t.loff.assign(off, off + n_keys + 1);
-        t.ids.assign(ids, ids + off[n_keys]);
-        if (t.ids.empty()) t.ids.push_back(0);
-        return t;
-    }
-    std::map<std::vector<uint16_t>, uint32_t> uniq;
-    std::vector<uint32_t> num(n_keys);
-    t.loff.push_back(0);
-    for (size_t i = 0; i < n_keys; ++i) {
-        std::vector<uint16_t> l(ids + off[i], ids + off[i + 1]);
-        auto it = uniq.find(l);
-        if (it == uniq.end()) {
-            it = uniq.emplace(l, (uint32_t)uniq.size()).first;
-            t.ids.insert(t.ids.end(), l.begin(), l.end());
-            t.loff.push_back((uint32_t)t.ids.size());
-        }
-        num[i] = it->second;
-    }
-    const size_t n = uniq.size();
-    t.w = n <= 256 ? 1u : (n <= 65536 ? 2u : 4u);
-    t.ix.resize(n_keys * t.w);
-    for (size_t i = 0; i < n_keys; ++i) std::memcpy(t.ix.data() + i * t.w, &num[i], t.w);   // little endian
-    if (t.ids.empty()) t.ids.push_back(0);
-    return t;
-}
 
-// packs `parts` (16-byte aligned sections) into one image and uploads it
-static bool make_image(const std::vector<std::pair<const void*, size_t>>& parts, DevImage& out) {
-    if (parts.size() > (size_t)IMG_MAX) return false;
-    size_t off = 0;
-    for (size_t i = 0; i < parts.size(); ++i) {
-        out.li.off[i] = (uint32_t)off;
-        off += (parts[i].second + 15) & ~(size_t)15;
-    }
-    if (off == 0) off = 16;
-    out.li.total = (uint32_t)off;
-    out.global = off > IMG_LDS_MAX;
-    std::vector<uint8_t> img(off, 0);
-    for (size_t i = 0; i < parts.size(); ++i)
-        if (parts[i].second) std::memcpy(img.data() + out.li.off[i], parts[i].first, parts[i].second);
-    return hipMalloc(reinterpret_cast<void**>(&out.d), off) == hipSuccess &&
-           hipMemcpy(out.d, img.data(), off, hipMemcpyHostToDevice) == hipSuccess;
-}
+// every PII_* environment knob, read once at the top of pii_engine_create (read_knobs)
+struct EngineKnobs {
+    RuleKnobs rules;
+    bool verbose = false;              // PII_VERBOSE: the images' sizes to stderr
+    uint32_t eval_split = 0;           // PII_EVAL_SPLIT: k_pair_eval work units per k_pair_first workgroup; 0 until
+                                       // create sets it by the size of the rule set
+    uint32_t merge_cap = MERGE_EVW;    // PII_MERGE_CAP: k_pairs_merge: events a wavefront stages (0: walk)
+    bool scan_count = true;            // PII_SCAN_COUNT=0: the count pass counts each lane's pairs, not the scan kernels
+    bool long_gate = true;             // PII_LONG_GATE=0: every call launches the long-row kernels
+    bool scan_ilv = true;              // PII_SCAN_ILV: k_scan grids of <= n_cu workgroups deal wavefronts round-robin
+    uint32_t win_long = 0;             // PII_WIN_LONG: incremental re-scan: rows longer than this many lanes are cut (0: never)
+    uint32_t halo_items = HALO_ITEMS;  // PII_HALO_ITEMS: k_win_halo's item list per workgroup (tests)
+    int timing = 1;                    // PII_TIMING: what a call records with HIP events (pii_set_timing)
+    uint32_t scan_streams = SCAN_STREAMS;   // PII_SCAN_STREAMS: streams for the SCAN groups' passes
+};
 
 struct pii_engine {
     int device = 0;
+    EngineKnobs k;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
@@ -4988,7 +4809,7 @@ struct pii_engine {
     size_t cap_bsum = 0;
     Event* ev = nullptr;
     pii_span* fd = nullptr;
-    uint32_t *n_ev = nullptr, *n_find = nullptr, *out_len = nullptr, *incl = nullptr, *agg_f = nullptr;
+    uint32_t *n_ev = nullptr, *out_len = nullptr, *incl = nullptr, *agg_f = nullptr;
     uint32_t* first_utt = nullptr;
     uint4* lane_geo = nullptr;         // per lane geometry (Geo::lanes)
     uint32_t* lane_perm = nullptr;     // k_scan slot -> lane (longest lanes first)
@@ -4996,20 +4817,16 @@ struct pii_engine {
     uint32_t* lane_bkt = nullptr;      // [2 * LANE_NB] bucket counts + reservation cursors
     uint32_t* lane_cnt = nullptr;
     uint64_t* bnd = nullptr;
-    bool scan_count = true;            // the scan kernels count each lane's pairs (PII_SCAN_COUNT=0: the count pass does)
     // The long-row gate (launch_front): whether a workload has rows that get cut is a property of the
     // workload, not of one batch, so a scan-and-redact call launches the long-row kernels only while cut
     // rows are expected.  A cut row in a call without them sets ERR_LONG and pii_sync runs the call again.
-    bool long_gate = true;             // PII_LONG_GATE=0: every call launches the long-row kernels
+    // (EngineKnobs::long_gate = false: every call launches the long-row kernels)
     bool long_expect = false;          // the next call launches them
     uint32_t long_idle = 0;            // completed calls in a row without a cut row
     bool last_gated = false;           // the last call was one the gate applies to
     bool gate_pending = false;         // ... and pii_sync has not yet taken its cut-row count into the state
     bool last_long_launched = true;    // ... and launched the long-row kernels
     uint32_t last_reruns = 0;          // re-runs the last pii_sync did
-    uint32_t halo_items = HALO_ITEMS;  // k_win_halo's item list per workgroup (PII_HALO_ITEMS: tests)
-    bool scan_ilv = true;              // k_scan grids of <= n_cu workgroups deal wavefronts round-robin (PII_SCAN_ILV)
-    uint32_t win_long = 0;             // incremental re-scan: rows longer than this many lanes are cut (PII_WIN_LONG; 0: never)
     EvLoc* evloc = nullptr;
     uint64_t ev_cap = 0;
     uint64_t* lane_ev = nullptr;      // exclusive scan of lane_cnt: first dense event index per lane
@@ -5023,8 +4840,6 @@ struct pii_engine {
     uint32_t* mcount = nullptr;   // matched pairs per k_pair_first wavefront segment
     FirstCont* cont = nullptr;
     uint32_t n_seg = 0;
-    uint32_t eval_split = 2;           // k_pair_eval work units per k_pair_first workgroup (PII_EVAL_SPLIT)
-    uint32_t merge_cap = MERGE_EVW;    // k_pairs_merge: events a wavefront stages (PII_MERGE_CAP; 0: walk)
     struct Call {
         const uint8_t* text;
         const uint64_t* offs;
@@ -5048,7 +4863,7 @@ struct pii_engine {
     int32_t* kw = nullptr;
     int16_t* ctx = nullptr;
     int32_t *agg_v = nullptr, *commit = nullptr;
-    uint64_t *span_offs = nullptr, *bsum = nullptr, *out_offs_tmp = nullptr;
+    uint64_t* bsum = nullptr;
     unsigned long long *lb_state = nullptr, *lb_ticket = nullptr;   // single-pass scan tiles / ticket counter
     uint32_t lb_cap = 0, lb_epoch = 0;
     uint32_t* d_err = nullptr;            // counter block (one memset per call): err, long_count, ncommit, pair_count
@@ -5063,6 +4878,7 @@ struct pii_engine {
     uint8_t *h_text = nullptr, *h_role = nullptr, *h_out = nullptr;
     uint64_t *h_offs = nullptr, *h_out_offs = nullptr;
     uint32_t* h_slot = nullptr;
+    std::vector<uint64_t> rel;         // the batch-relative offsets on their way to h_offs
     int64_t* h_ts = nullptr;
     pii_span* h_spans = nullptr;
     int16_t* h_ctx = nullptr;
@@ -5071,12 +4887,11 @@ struct pii_engine {
     uint64_t cap_h_ext = 0;
     uint32_t cap_h_ext_n = 0;
     hipEvent_t tev[7] = {};
-    // what a call records with HIP events (pii_set_timing): 0 = only the completion event; 1 = + the
+    // k.timing, what a call records with HIP events (pii_set_timing): 0 = only the completion event; 1 = + the
     // call's start and the events around k_scan / k_redact (the roofline kernels); 2 = + the stage
     // boundaries (pii_last_timings [0..4]).  An event record between two kernels costs ~6 us of GPU
     // time (the queue drains at the marker): level 2's five stage events were ~30 us of a config-2
     // step and ~12% of a window re-scan step (rocprofv3 kernel trace gaps).
-    int timing = 1;
     float last_ms[6] = {};
     hipEvent_t kev[4] = {};           // around k_scan and k_redact (the roofline kernels)
     bool kev_valid = false;
@@ -5085,9 +4900,7 @@ struct pii_engine {
     // window re-scan (a12): resident history rings + per-call scratch
     uint32_t win_n = 0, win_slot_bytes = 0;
     bool window_ok = false;
-    WDesc* wr_desc = nullptr;
-    uint32_t *wr_cnt = nullptr, *wr_head = nullptr;
-    uint8_t* wr_arena = nullptr;
+    WinTables wr;
     WCand* wc = nullptr;
     uint32_t* phot = nullptr;
     uint64_t wc_cap = 0;
@@ -5383,36 +5196,117 @@ size_t hist_bytes(const pii_engine* e) { return 64 + (size_t)std::max(e->R.T, 25
 // long_kernels = false (the long-row gate is closed): k_fill_long and k_scan_fix are not launched,
 // and k_chunk_index fails the call with ERR_LONG if it meets a cut row after all.
 constexpr uint32_t LONG_IDLE_CALLS = 8;      // calls without a cut row after which the gate closes again
-int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint32_t n_utt, uint32_t n_chunks,
-                 uint64_t base, uint64_t total_bytes, const uint32_t* slot, const uint8_t* role, const int64_t* ts,
-                 int16_t* ctx, int16_t* win_ctx, const unsigned long long* pcount, hipStream_t st,
-                 bool long_kernels, const uint32_t* err_init = nullptr, bool ctx_kernels = true,
-                 bool pair_first = true) {
+
+using Call = pii_engine::Call;
+
+// What a run_* function asks of begin_call: everything in which the four paths' prologues differ.
+enum : unsigned { ENS_QUEUES = 1, ENS_REDACT = 2, ENS_WINDOW = 4, ENS_JOIN = 8 };
+enum Flag { F_CLEAR, F_SET, F_KEEP };     // a flag the call clears, sets, or leaves as the last call set it
+struct CallPlan {
+    int kind;             // last_kind: what pii_sync re-runs; -1: a second pass, e->last stays the first's
+    uint32_t cut_lanes;   // rows longer than this many lanes are cut (long_min); 0: no row is
+    int min_len;          // findings arenas hold one finding per min_len bytes; 0: the rules' shortest match
+    unsigned ensure;      // ENS_*: the work buffers the path needs beyond ensure_scratch's
+    Flag gated;           // last_gated / gate_pending: the long-row gate applies (only where rows can be cut)
+    Flag kev;             // kev_valid: YES = the call has rows and bytes, so k_scan and k_redact run
+};
+// ... and what it hands back
+struct CallGeo {
+    uint32_t n_chunks;
+    const unsigned long long* pcount;      // the pair queue's length, on the device
+    Geo g;
+};
+
+int ensure_queues(pii_engine* e, uint64_t total_bytes);
+int ensure_window_scratch(pii_engine* e, uint32_t n_utt);
+int ensure_join(pii_engine* e, uint32_t n_utt);
+
+// The prologue of every call: size check, lane geometry (slices are aligned to the address of the
+// batch's first byte, text + base; a context-only call's record has base 0), work buffers, the record
+// pii_sync re-runs.
+int begin_call(pii_engine* e, const Call& c, const CallPlan& p, CallGeo& cg) {
+    if (c.total > PII_MAX_BATCH_BYTES || c.total + 2ull * c.n_utt + (c.total >> MIN_LANE_SHIFT) > 0xFFFFFFF0ull) {
+        e->err = "batch larger than PII_MAX_BATCH_BYTES (positions and event arenas are 32-bit); split it";
+        return PII_E_ARG;
+    }
+    e->lane_shift = pick_lane_shift(e, c.total);
+    e->r0 = (uint32_t)(((uintptr_t)c.text + c.base) & 63);
+    e->long_min = p.cut_lanes ? p.cut_lanes << e->lane_shift : NO_CUTS;
+    cg.n_chunks = lane_count(e, c.total);
+    e->last_lanes = cg.n_chunks;
+    int rc = ensure_scratch(e, c.n_utt, c.total, cg.n_chunks, p.min_len);
+    if (rc || ((p.ensure & ENS_QUEUES) && (rc = ensure_queues(e, c.total))) ||
+        ((p.ensure & ENS_REDACT) && (rc = ensure_redact(e, c.span_cap, c.out_cap))) ||
+        ((p.ensure & ENS_WINDOW) && (rc = ensure_window_scratch(e, c.n_utt))) ||
+        ((p.ensure & ENS_JOIN) && (rc = ensure_join(e, c.n_utt))))
+        return rc;
+    if (p.kind >= 0) {
+        e->last = c;
+        e->last_kind = p.kind;
+    }
+    if (p.gated != F_KEEP) e->last_gated = e->gate_pending = p.gated == F_SET && e->long_min != NO_CUTS;
+    if (p.kev != F_KEEP) e->kev_valid = p.kev == F_SET && c.n_utt > 0 && c.total > 0;
+    // queue length = the lane-count scan's total (lane_pair[n_chunks]); 0 for an empty batch
+    cg.pcount = cg.n_chunks > 0 ? reinterpret_cast<const unsigned long long*>(e->lane_pair + cg.n_chunks) : e->pair_count;
+    cg.g = make_geo(e, c.offs, c.n_utt, cg.n_chunks, c.base);
+    return PII_OK;
+}
+
+// The epilogue: the totals (and `bytes` - 64 of the histogram behind them) to the pinned copy, the
+// completion event.
+int end_call(pii_engine* e, hipStream_t st, size_t bytes, bool hist_valid) {
+    if (e->k.timing >= 2) HIPCHK(hipEventRecord(e->tev[5], st));
+    HIPCHK(hipMemcpyAsync(e->h_totals, e->d_totals, bytes, hipMemcpyDeviceToHost, st));
+    e->h_hist_valid = hist_valid;
+    HIPCHK(hipEventRecord(e->tev[6], st));
+    return PII_OK;
+}
+
+// write the per-conversation context of n rows back (a no-op on the device when the call failed)
+void launch_ctx_commit(pii_engine* e, uint32_t n, const uint32_t* slot, const int32_t* kw, const int64_t* ts,
+                       hipStream_t st) {
+    k_ctx_commit<<<std::min<uint32_t>((n + 255) / 256, 4 * e->n_cu), 256, 0, st>>>(
+        slot, kw, ts, e->incl, e->ncommit, e->commit, e->d_err, e->st_group, e->st_ts);
+}
+
+struct Front {
+    int16_t* ctx;                          // the rows' context groups (k_ctx_apply's output)
+    int16_t* win_ctx;                      // ... and each row's window's, on the window paths
+    bool long_kernels;
+    const uint32_t* err_init = nullptr;    // a second pass: the first pass's counter block
+    bool ctx_kernels = true;
+    bool pair_first = true;
+};
+
+int launch_front(pii_engine* e, const Call& c, const CallGeo& cg, const Front& f) {
+    const auto [ctx, win_ctx, long_kernels, err_init, ctx_kernels, pair_first] = f;
+    const uint32_t n_chunks = cg.n_chunks;
+    const unsigned long long* pcount = cg.pcount;
+    const Geo& g = cg.g;
     const RulesDev& R = e->R;
     e->epoch += 1;
     const bool long_k = long_kernels && e->long_min != NO_CUTS;
-    const Geo g = make_geo(e, offs, n_utt, n_chunks, base);
     // counter block (a second pass over the call starts from the first pass's), lane buckets, and the
     // histogram if pii_histogram_reset was called since the last call
-    k_begin<<<1, 256, 0, st>>>(e->d_err, err_init, e->lane_bkt, n_chunks > 0 ? 2u * LANE_NB : 0u, e->hist,
+    k_begin<<<1, 256, 0, c.st>>>(e->d_err, err_init, e->lane_bkt, n_chunks > 0 ? 2u * LANE_NB : 0u, e->hist,
                                e->hist_zero_pending ? (uint32_t)std::max(e->R.T, 256) : 0u);
     e->hist_zero_pending = false;
-    if (e->timing >= 1) HIPCHK(hipEventRecord(e->tev[0], st));
-    if (n_utt > 0) {
-        k_chunk_index<<<(n_utt / CI_ROWS + 1 + 255) / 256, 256, 0, st>>>(offs, role, n_utt, n_chunks, e->lane_shift, e->r0,
+    if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->tev[0], c.st));
+    if (c.n_utt > 0) {
+        k_chunk_index<<<(c.n_utt / CI_ROWS + 1 + 255) / 256, 256, 0, c.st>>>(c.offs, c.role, c.n_utt, n_chunks, e->lane_shift, e->r0,
                                                                 e->long_min, R.kw_always_min, e->first_utt,
                                                                 e->out_len, e->kw, win_ctx ? e->wc_n : nullptr,
-                                                                e->long_rows, e->long_count, (uint32_t)e->cap_long, base,
-                                                                total_bytes, e->d_err, long_kernels);
+                                                                e->long_rows, e->long_count, (uint32_t)e->cap_long, c.base,
+                                                                c.total, e->d_err, long_kernels);
         if (long_k)
-            k_fill_long<<<row_grid(e, total_bytes), 256, 0, st>>>(offs, n_utt, n_chunks, e->lane_shift, e->r0, e->long_rows,
+            k_fill_long<<<row_grid(e, c.total), 256, 0, c.st>>>(c.offs, c.n_utt, n_chunks, e->lane_shift, e->r0, e->long_rows,
                                                                    e->long_count, (uint32_t)e->cap_long, e->first_utt);
         if (n_chunks > 0) {
             const uint32_t nsb = (n_chunks + LANE_SORT_CHUNK - 1) / LANE_SORT_CHUNK;
             Geo g0 = g;
             g0.lanes = nullptr;
-            k_lane_count<<<nsb, 256, 0, st>>>(g0, e->lane_bkt, e->lane_geo);
-            k_lane_place<<<nsb, 256, 0, st>>>(g, e->lane_bkt, e->lane_perm, e->lane_pos);
+            k_lane_count<<<nsb, 256, 0, c.st>>>(g0, e->lane_bkt, e->lane_geo);
+            k_lane_place<<<nsb, 256, 0, c.st>>>(g, e->lane_bkt, e->lane_perm, e->lane_pos);
             // one pass per SCAN group (one for the shipped rules): scan, then the stitching; the
             // utterance-start words are written once.  Several groups: group q on stream q mod
             // SCAN_STREAMS (forked after the words, joined before the pairs), so one pass's tail -- the
@@ -5424,7 +5318,7 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
             // -- the write pass records the keyword groups.  Several groups add their counts up in the
             // count pass, and a call without a pair queue has no other producer of the keyword groups:
             // both keep it.
-            const bool scan_count = e->scan_count && e->n_sg == 1 && pair_first;
+            const bool scan_count = e->k.scan_count && e->n_sg == 1 && pair_first;
             uint32_t* const scan_np = scan_count ? e->lane_np : nullptr;
             for (uint32_t q = 0; q < e->n_sg; ++q) {
                 const RulesDev& Rq = e->sg[q];
@@ -5432,15 +5326,15 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                 uint32_t* cq = e->lane_cnt + (uint64_t)q * e->cap_lanes;
                 uint32_t* stq = e->lane_st + 2ull * q * e->cap_lanes;
                 if (q == 0) {
-                    k_lane_bits<<<(n_chunks + 255) / 256, 256, 0, st>>>(g, e->lane_pos, e->bnd);
-                    if (e->timing >= 1) HIPCHK(hipEventRecord(e->kev[0], st));
+                    k_lane_bits<<<(n_chunks + 255) / 256, 256, 0, c.st>>>(g, e->lane_pos, e->bnd);
+                    if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->kev[0], c.st));
                     if (two) {
-                        HIPCHK(hipEventRecord(e->ev_fork, st));
+                        HIPCHK(hipEventRecord(e->ev_fork, c.st));
                         for (uint32_t i = 0; i + 1 < ns_scan; ++i) HIPCHK(hipStreamWaitEvent(e->aux[i], e->ev_fork, 0));
                     }
                 }
                 const uint32_t si = q % ns_scan;
-                const hipStream_t sq = si ? e->aux[si - 1] : st;
+                const hipStream_t sq = si ? e->aux[si - 1] : c.st;
                 // a WIDE table (row offsets / 2) that still leaves room for two workgroups per CU runs
                 // at 768 threads too: 6 waves/SIMD instead of 4 (config 5: the 262 regex types' 70 KB
                 // table); only the dictionary groups' ~100 KB tables need one 1024-thread workgroup
@@ -5448,30 +5342,30 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                 const int nt = one_wg ? SCAN_BLOCK_WIDE : SCAN_BLOCK;
                 const uint32_t nb = (n_chunks + nt - 1) / nt;
                 (q == 0 ? k_scan<true> : one_wg ? k_scan<false, SCAN_BLOCK_WIDE> : k_scan<false>)<<<
-                    nb, nt, e->sg_lds[q], sq>>>(Rq, g, text, e->bnd, e->lane_perm, evq, cq, stq, e->d_err,
-                                                e->scan_ilv && nb <= e->n_cu ? nb : 0u, scan_np);
+                    nb, nt, e->sg_lds[q], sq>>>(Rq, g, c.text, e->bnd, e->lane_perm, evq, cq, stq, e->d_err,
+                                                e->k.scan_ilv && nb <= e->n_cu ? nb : 0u, scan_np);
             }
             for (uint32_t i = 0; i + 1 < ns_scan; ++i) {
                 HIPCHK(hipEventRecord(e->ev_join[i], e->aux[i]));
-                HIPCHK(hipStreamWaitEvent(st, e->ev_join[i], 0));
+                HIPCHK(hipStreamWaitEvent(c.st, e->ev_join[i], 0));
             }
-            if (e->timing >= 1) HIPCHK(hipEventRecord(e->kev[1], st));
+            if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->kev[1], c.st));
             if (long_k)
-                k_scan_fix<<<dim3(row_grid(e, total_bytes), e->n_sg), 256, e->max_sg_lds + FIX_LDS, st>>>(
-                    e->d_sg, e->d_sg_lds, g, text, e->long_rows, e->long_count, e->ev, e->cap_ev, e->lane_cnt,
+                k_scan_fix<<<dim3(row_grid(e, c.total), e->n_sg), 256, e->max_sg_lds + FIX_LDS, c.st>>>(
+                    e->d_sg, e->d_sg_lds, g, c.text, e->long_rows, e->long_count, e->ev, e->cap_ev, e->lane_cnt,
                     e->lane_st, e->cap_lanes, e->d_err, scan_np);
             const uint32_t nbp = (n_chunks + PAIRS_BLOCK - 1) / PAIRS_BLOCK;
             const bool multi = e->n_sg > 1;
             const uint32_t ns = e->n_sg, cs = (uint32_t)e->cap_lanes;
             const uint64_t es = e->cap_ev;
-            if (multi) HIPCHK(hipMemsetAsync(e->lane_np, 0, (size_t)n_chunks * sizeof(uint32_t), st));
+            if (multi) HIPCHK(hipMemsetAsync(e->lane_np, 0, (size_t)n_chunks * sizeof(uint32_t), c.st));
             if (!scan_count)
-                k_pairs_flat<false><<<dim3(nbp, ns), PAIRS_BLOCK, 0, st>>>(R, g, e->ev, e->lane_cnt, role, e->kw, e->evloc,
+                k_pairs_flat<false><<<dim3(nbp, ns), PAIRS_BLOCK, 0, c.st>>>(R, g, e->ev, e->lane_cnt, c.role, e->kw, e->evloc,
                                                                            e->pair_cap, e->ev_cap, e->lane_pair,
                                                                            e->lane_ev, e->lane_np, e->d_err, e->pres, e->acct,
                                                                            ns, es, cs, e->lane_evn);
             int rc;
-            if ((rc = exclusive_scan(e, e->lane_np, n_chunks, e->lane_pair, st, multi ? e->lane_evn : e->lane_cnt,
+            if ((rc = exclusive_scan(e, e->lane_np, n_chunks, e->lane_pair, c.st, multi ? e->lane_evn : e->lane_cnt,
                                      n_chunks, e->lane_ev)))
                 return rc;
             // (no pair queue when no FIRST runs follow: the first pass of a full window re-scan and a
@@ -5479,38 +5373,38 @@ int launch_front(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
             if (!pair_first) {
             } else if (multi) {
                 const uint32_t lpb = MERGE_WAVES * MERGE_LPW;
-                k_pairs_merge<<<(n_chunks + lpb - 1) / lpb, MERGE_WAVES * 64, 0, st>>>(
+                k_pairs_merge<<<(n_chunks + lpb - 1) / lpb, MERGE_WAVES * 64, 0, c.st>>>(
                     g, e->ev, e->lane_cnt, e->evloc, e->pres, R.d_acc_off, R.d_acc_ids, e->pair_cap, e->ev_cap,
-                    e->lane_pair, e->lane_ev, e->lane_np, e->d_err, ns, es, cs, e->acct, e->merge_cap);
+                    e->lane_pair, e->lane_ev, e->lane_np, e->d_err, ns, es, cs, e->acct, e->k.merge_cap);
             } else {
-                (scan_count ? k_pairs_flat<true, true> : k_pairs_flat<true>)<<<nbp, PAIRS_BLOCK, 0, st>>>(
-                    R, g, e->ev, e->lane_cnt, role, e->kw, e->evloc, e->pair_cap, e->ev_cap, e->lane_pair, e->lane_ev,
+                (scan_count ? k_pairs_flat<true, true> : k_pairs_flat<true>)<<<nbp, PAIRS_BLOCK, 0, c.st>>>(
+                    R, g, e->ev, e->lane_cnt, c.role, e->kw, e->evloc, e->pair_cap, e->ev_cap, e->lane_pair, e->lane_ev,
                     e->lane_np, e->d_err, e->pres, e->acct, 1, 0, 0, nullptr);
             }
         }
         HIPCHK(hipGetLastError());
     }
-    if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[1], st));
-    const uint32_t nblk = (uint32_t)(((uint64_t)n_utt + CTX_TILE - 1) / CTX_TILE);
-    if (n_utt > 0 && ctx_kernels) {
+    if (e->k.timing >= 2) HIPCHK(hipEventRecord(e->tev[1], c.st));
+    const uint32_t nblk = (uint32_t)(((uint64_t)c.n_utt + CTX_TILE - 1) / CTX_TILE);
+    if (c.n_utt > 0 && ctx_kernels) {
         // 16-byte row groups when the caller's arrays allow it
-        const bool vec = ((uintptr_t)slot & 15) == 0 && ((uintptr_t)role & 7) == 0 && ((uintptr_t)ts & 15) == 0 &&
+        const bool vec = ((uintptr_t)c.slot & 15) == 0 && ((uintptr_t)c.role & 7) == 0 && ((uintptr_t)c.ts & 15) == 0 &&
                          ((uintptr_t)ctx & 15) == 0 && ((uintptr_t)win_ctx & 15) == 0;
-        (vec ? k_ctx_scan<true> : k_ctx_scan<false>)<<<nblk, CTX_THREADS, 0, st>>>(
-            slot, role, e->kw, n_utt, e->n_slots, e->agg_v, e->agg_f, e->stamp, e->epoch, e->d_err);
-        (vec ? k_ctx_apply<true> : k_ctx_apply<false>)<<<nblk, CTX_THREADS, 0, st>>>(
-            slot, role, e->kw, ts, n_utt, e->n_slots, e->ttl_us, e->agg_v, e->agg_f, e->st_group, e->st_ts, ctx,
+        (vec ? k_ctx_scan<true> : k_ctx_scan<false>)<<<nblk, CTX_THREADS, 0, c.st>>>(
+            c.slot, c.role, e->kw, c.n_utt, e->n_slots, e->agg_v, e->agg_f, e->stamp, e->epoch, e->d_err);
+        (vec ? k_ctx_apply<true> : k_ctx_apply<false>)<<<nblk, CTX_THREADS, 0, c.st>>>(
+            c.slot, c.role, e->kw, c.ts, c.n_utt, e->n_slots, e->ttl_us, e->agg_v, e->agg_f, e->st_group, e->st_ts, ctx,
             e->commit, e->incl, e->ncommit, win_ctx);
         HIPCHK(hipGetLastError());
     }
-    if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[2], st));
-    if (n_utt > 0 && n_chunks > 0 && pair_first) {
+    if (e->k.timing >= 2) HIPCHK(hipEventRecord(e->tev[2], c.st));
+    if (c.n_utt > 0 && n_chunks > 0 && pair_first) {
         (e->img_first.global ? k_pair_first<true> : k_pair_first<false>)<<<e->n_seg, PAIR_BLOCK,
                                                                             e->img_first.global
                                                                                 ? e->img_first_hot.li.total
                                                                                 : e->img_first.lds(),
-                                                                            st>>>(
-            e->img_first.d, e->img_first.li, text, offs, pcount, e->pair_cap, e->evloc, e->pres, e->pend, e->matched,
+                                                                            c.st>>>(
+            e->img_first.d, e->img_first.li, c.text, c.offs, pcount, e->pair_cap, e->evloc, e->pres, e->pend, e->matched,
             e->cont, e->mcount, e->d_err, e->img_first_hot.d, e->img_first_hot.li, e->first_p_hot);
         HIPCHK(hipGetLastError());
     }
@@ -5532,68 +5426,52 @@ struct WinFull {
     uint32_t n_new;
 };
 
-int run_pipeline(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint32_t n_utt, uint64_t base,
-                 uint64_t total_bytes, const uint32_t* slot, const uint8_t* role, const int64_t* ts, uint8_t* out,
-                 uint64_t out_cap, uint64_t* out_offs, pii_span* spans, uint32_t span_cap, int16_t* ctx_info,
-                 hipStream_t st, const pii_span* ext = nullptr, const uint32_t* ext_n = nullptr,
-                 uint32_t ext_stride = 0, const WinFull* wf = nullptr) {
-    if (total_bytes > PII_MAX_BATCH_BYTES || total_bytes + 2ull * n_utt + (total_bytes >> MIN_LANE_SHIFT) > 0xFFFFFFF0ull) {
-        e->err = "batch larger than PII_MAX_BATCH_BYTES (positions and event arenas are 32-bit); split it";
-        return PII_E_ARG;
-    }
-    const bool has_ext = ext != nullptr && n_utt > 0;
-    if (has_ext && (!ext_n || ext_stride == 0)) {
+// pii_scan_redact*: the whole pipeline.  wf: as the second pass of a full window re-scan (a window call
+// keeps its own record for pii_sync's re-run).
+int run_pipeline(pii_engine* e, const Call& c, const WinFull* wf = nullptr) {
+    const bool has_ext = c.ext != nullptr && c.n_utt > 0;
+    if (has_ext && (!c.ext_n || c.ext_stride == 0)) {
         e->err = "external spans need their per-row counts and a stride > 0";
         return PII_E_ARG;
     }
-    e->lane_shift = pick_lane_shift(e, total_bytes);
-    e->r0 = (uint32_t)(((uintptr_t)text + base) & 63);
-    e->long_min = 2u << e->lane_shift;          // rows longer than two lanes are cut
-    const uint32_t n_chunks = lane_count(e, total_bytes);
-    e->last_lanes = n_chunks;
-    // external spans can be 1 byte long: the findings arenas are sized (and placed) for that
+    // rows longer than two lanes are cut; external spans can be 1 byte long: the findings arenas are
+    // sized (and placed) for that; the long-row gate: plain scan-and-redact calls only (the window
+    // paths always launch)
+    CallGeo cg;
+    const CallPlan plan{/*kind*/ wf ? -1 : 0, /*cut_lanes*/ 2, /*min_len*/ has_ext ? 1 : 0, ENS_QUEUES | ENS_REDACT,
+                        /*gated*/ wf ? F_CLEAR : F_SET, /*kev*/ F_SET};
+    int rc = begin_call(e, c, plan, cg);
+    if (rc) return rc;
+    const uint32_t n_chunks = cg.n_chunks;
+    const unsigned long long* pcount = cg.pcount;
+    const Geo& g = cg.g;
     RulesDev Rsel = e->R;
     if (has_ext) Rsel.min_len = 1;
-    int rc = ensure_scratch(e, n_utt, total_bytes, n_chunks, Rsel.min_len);
-    if (rc || (rc = ensure_queues(e, total_bytes)) || (rc = ensure_redact(e, span_cap, out_cap))) return rc;
-    if (!wf) {                  // (a window call keeps its own record for pii_sync's re-run)
-        e->last = pii_engine::Call{text, offs, n_utt, base, total_bytes, slot, role, ts, out, out_cap, out_offs, spans,
-                                   span_cap, ctx_info, st, ext, ext_n, ext_stride};
-        e->last_kind = 0;
-    }
-    // the long-row gate: plain scan-and-redact calls only (the window paths always launch)
-    e->last_gated = e->gate_pending = !wf && e->long_min != NO_CUTS;
-    const bool long_k = !e->last_gated || !e->long_gate || e->long_expect;
+    const bool long_k = !e->last_gated || !e->k.long_gate || e->long_expect;
     e->last_long_launched = long_k;
     const RulesDev& R = e->R;
-    int16_t* ctx = wf ? const_cast<int16_t*>(wf->ctx_given) : ctx_info ? ctx_info : e->ctx;
-    e->kev_valid = n_utt > 0 && total_bytes > 0;
-    const Geo g = make_geo(e, offs, n_utt, n_chunks, base);
-    // queue length = the lane-count scan's total (lane_pair[n_chunks]); 0 for an empty batch
-    const unsigned long long* pcount =
-        n_chunks > 0 ? reinterpret_cast<const unsigned long long*>(e->lane_pair + n_chunks) : e->pair_count;
-    if ((rc = launch_front(e, text, offs, n_utt, n_chunks, base, total_bytes, slot, role, ts, ctx, nullptr, pcount,
-                           st, long_k, wf ? wf->err_init : nullptr, wf == nullptr)))
+    int16_t* ctx = wf ? const_cast<int16_t*>(wf->ctx_given) : c.ctx_info ? c.ctx_info : e->ctx;
+    if ((rc = launch_front(e, c, cg, {ctx, nullptr, long_k, wf ? wf->err_init : nullptr, wf == nullptr})))
         return rc;
-    if (n_utt > 0 && n_chunks > 0) {
+    if (c.n_utt > 0 && n_chunks > 0) {
         if (e->img_eval_rg.d) {
-            k_pair_eval<false, true><<<e->n_seg * e->eval_split, PAIR_BLOCK, e->img_eval_rg.lds(), st>>>(
-                e->img_eval_rg.d, e->img_eval_rg.li, R.T, text, offs, role, ctx, pcount, e->pair_cap, e->matched,
+            k_pair_eval<false, true><<<e->n_seg * e->k.eval_split, PAIR_BLOCK, e->img_eval_rg.lds(), c.st>>>(
+                e->img_eval_rg.d, e->img_eval_rg.li, R.T, c.text, c.offs, c.role, ctx, pcount, e->pair_cap, e->matched,
                 e->mcount, e->n_seg, e->evloc, e->pend, e->pres, reinterpret_cast<SelRec*>(e->cont), R.rule_off,
-                R.rule_ids, e->eval_split);
+                R.rule_ids, e->k.eval_split);
         } else {
             (e->img_eval.global ? (e->lists_cl ? k_pair_eval<true, false, true> : k_pair_eval<true>)
                                 : (e->lists_cl ? k_pair_eval<false, false, true> : k_pair_eval<false>))<<<
-                e->n_seg * e->eval_split, PAIR_BLOCK,
-                                                                             e->img_eval.lds(), st>>>(
-                e->img_eval.d, e->img_eval.li, R.T, text, offs, role, ctx, pcount, e->pair_cap, e->matched,
+                e->n_seg * e->k.eval_split, PAIR_BLOCK,
+                                                                             e->img_eval.lds(), c.st>>>(
+                e->img_eval.d, e->img_eval.li, R.T, c.text, c.offs, c.role, ctx, pcount, e->pair_cap, e->matched,
                 e->mcount, e->n_seg, e->evloc, e->pend, e->pres, reinterpret_cast<SelRec*>(e->cont), nullptr, nullptr,
-                e->eval_split);
+                e->k.eval_split);
         }
         const bool xg = e->img_sel_rg.d != nullptr;
         const DevImage& isel = xg ? e->img_sel_rg : e->img_sel;
-        const SelIO io{e->lane_pair, e->lane_np, reinterpret_cast<const SelRec*>(e->cont), e->pend, e->pair_cap, role, ctx, e->fd,
-                       e->lane_nf, e->lane_rd, e->lane_reach, e->out_len, e->spill, ext, ext_n, ext_stride, e->d_err,
+        const SelIO io{e->lane_pair, e->lane_np, reinterpret_cast<const SelRec*>(e->cont), e->pend, e->pair_cap, c.role, ctx, e->fd,
+                       e->lane_nf, e->lane_rd, e->lane_reach, e->out_len, e->spill, c.ext, c.ext_n, c.ext_stride, e->d_err,
                        xg ? R.excl_off : nullptr, xg ? R.excl_ids : nullptr};
         const bool gi = isel.global;
         // (CL: the images hold deduplicated exclusion lists -- a large rule set; the RG path reads the
@@ -5607,81 +5485,75 @@ int run_pipeline(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint3
                                   : (gi ? k_sel_fix<true, false, true> : k_sel_fix<false, false, true>))
                        : (has_ext ? (gi ? k_sel_fix<true, true> : k_sel_fix<false, true>)
                                   : (gi ? k_sel_fix<true, false> : k_sel_fix<false, false>));
-        ksel<<<(n_chunks + 255) / 256, 256, isel.lds(), st>>>(Rsel, isel.d, isel.li, g, io, e->d_err);
+        ksel<<<(n_chunks + 255) / 256, 256, isel.lds(), c.st>>>(Rsel, isel.d, isel.li, g, io, e->d_err);
         if (long_k) {
-            const uint32_t rg = row_grid(e, total_bytes);
-            k_sel_dirty<<<rg, ROW_BLOCK, 0, st>>>(g, e->long_rows, e->long_count, e->lane_reach, e->dirty, e->d_err);
-            kfix<<<rg, 256, isel.lds(), st>>>(Rsel, isel.d, isel.li, g, io, e->long_rows, e->long_count, e->dirty,
+            const uint32_t rg = row_grid(e, c.total);
+            k_sel_dirty<<<rg, ROW_BLOCK, 0, c.st>>>(g, e->long_rows, e->long_count, e->lane_reach, e->dirty, e->d_err);
+            kfix<<<rg, 256, isel.lds(), c.st>>>(Rsel, isel.d, isel.li, g, io, e->long_rows, e->long_count, e->dirty,
                                               e->d_err);
-            k_rowlen<<<rg, ROW_BLOCK, 0, st>>>(g, e->long_rows, e->long_count, e->lane_rd, e->lane_rowbase, e->out_len,
+            k_rowlen<<<rg, ROW_BLOCK, 0, c.st>>>(g, e->long_rows, e->long_count, e->lane_rd, e->lane_rowbase, e->out_len,
                                                e->d_err);
         }
         HIPCHK(hipGetLastError());
     }
-    if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[3], st));
+    if (e->k.timing >= 2) HIPCHK(hipEventRecord(e->tev[3], c.st));
     // row output offsets and per-lane span offsets: one dual scan (a big batch: 3 launches instead of
     // 6; a small one: one single-pass look-back launch instead of 2)
     // (a big batch: k_scan_apply closes the call, as k_finalize does for a small one or a window's)
     const uint64_t* ev_count = n_chunks > 0 ? e->lane_ev + n_chunks : nullptr;
     bool fin_done = false;
     if (n_chunks > 0) {
-        const ScanFin fin{e->d_totals, e->d_err, pcount, ev_count, e->long_count, out_cap, span_cap};
-        if ((rc = exclusive_scan(e, e->out_len, n_utt, out_offs, st, e->lane_nf, n_chunks, e->lane_sp, wf ? nullptr : &fin,
+        const ScanFin fin{e->d_totals, e->d_err, pcount, ev_count, e->long_count, c.out_cap, c.span_cap};
+        if ((rc = exclusive_scan(e, e->out_len, c.n_utt, c.out_offs, c.st, e->lane_nf, n_chunks, e->lane_sp, wf ? nullptr : &fin,
                                  &fin_done)))
             return rc;
     } else {
-        if ((rc = exclusive_scan(e, e->out_len, n_utt, out_offs, st))) return rc;
-        if ((rc = exclusive_scan(e, e->lane_nf, n_chunks, e->lane_sp, st))) return rc;
+        if ((rc = exclusive_scan(e, e->out_len, c.n_utt, c.out_offs, c.st))) return rc;
+        if ((rc = exclusive_scan(e, e->lane_nf, n_chunks, e->lane_sp, c.st))) return rc;
     }
     if (!fin_done)
-        k_finalize<<<1, 1, 0, st>>>(out_offs, e->lane_sp, n_utt, n_chunks, out_cap, span_cap, e->d_err, e->d_totals,
+        k_finalize<<<1, 1, 0, c.st>>>(c.out_offs, e->lane_sp, c.n_utt, n_chunks, c.out_cap, c.span_cap, e->d_err, e->d_totals,
                                     pcount, ev_count, nullptr, e->long_count);
     HIPCHK(hipGetLastError());
-    if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[4], st));
-    if (n_utt > 0) {
+    if (e->k.timing >= 2) HIPCHK(hipEventRecord(e->tev[4], c.st));
+    if (c.n_utt > 0) {
         if (n_chunks > 0) {
             const uint32_t nsb = (n_chunks + 255) / 256;
-            k_spans<<<nsb, 256, 0, st>>>(Rsel, g, e->fd, e->lane_nf, e->lane_sp, e->lane_rowbase, out_offs, e->d_err,
-                                         spans, e->rsp, e->hist_part, e->hist_types);
-            const uint32_t tiles = (uint32_t)((out_cap + 15) >> RTILE_SHIFT) + 1;
-            k_tile_first<<<(tiles + 255) / 256, 256, 0, st>>>(R, e->rsp, e->lane_sp + n_chunks, out_offs + n_utt,
-                                                              (uint32_t)((uintptr_t)out & 15), tiles, e->d_err,
+            k_spans<<<nsb, 256, 0, c.st>>>(Rsel, g, e->fd, e->lane_nf, e->lane_sp, e->lane_rowbase, c.out_offs, e->d_err,
+                                         c.spans, e->rsp, e->hist_part, e->hist_types);
+            const uint32_t tiles = (uint32_t)((c.out_cap + 15) >> RTILE_SHIFT) + 1;
+            k_tile_first<<<(tiles + 255) / 256, 256, 0, c.st>>>(R, e->rsp, e->lane_sp + n_chunks, c.out_offs + c.n_utt,
+                                                              (uint32_t)((uintptr_t)c.out & 15), tiles, e->d_err,
                                                               e->tile_first);
-            if (e->timing >= 1) HIPCHK(hipEventRecord(e->kev[2], st));
-            (e->xf_src ? k_redact<true> : k_redact<false>)<<<tiles, REDACT_BLOCK, 0, st>>>(
-                R, text, offs, e->rsp, e->lane_sp + n_chunks, out_offs + n_utt, total_bytes, e->tile_first, e->d_err,
-                out);
+            if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->kev[2], c.st));
+            (e->xf_src ? k_redact<true> : k_redact<false>)<<<tiles, REDACT_BLOCK, 0, c.st>>>(
+                R, c.text, c.offs, e->rsp, e->lane_sp + n_chunks, c.out_offs + c.n_utt, c.total, e->tile_first, e->d_err,
+                c.out);
             if (e->xf_mask) {   // (a lane's findings arena holds one span per min_len bytes; no more than span_cap)
-                const uint64_t ms = std::min<uint64_t>(span_cap, total_bytes / (uint64_t)Rsel.min_len + n_chunks);
-                k_mask<<<(uint32_t)(ms / 256) + 1, 256, 0, st>>>(R, text, offs, e->rsp, e->lane_sp + n_chunks, e->d_err,
-                                                                 out);
+                const uint64_t ms = std::min<uint64_t>(c.span_cap, c.total / (uint64_t)Rsel.min_len + n_chunks);
+                k_mask<<<(uint32_t)(ms / 256) + 1, 256, 0, c.st>>>(R, c.text, c.offs, e->rsp, e->lane_sp + n_chunks, e->d_err,
+                                                                 c.out);
             }
             if (e->xf_hash) {   // (the same bound on the span count)
-                const uint64_t ms = std::min<uint64_t>(span_cap, total_bytes / (uint64_t)Rsel.min_len + n_chunks);
-                k_hash<<<(uint32_t)(ms / HASH_BLOCK) + 1, HASH_BLOCK, 0, st>>>(
-                    R.xf_kind, e->d_hash_key, e->d_hash_mid, text, offs, e->rsp, e->lane_sp + n_chunks, e->d_err, out);
+                const uint64_t ms = std::min<uint64_t>(c.span_cap, c.total / (uint64_t)Rsel.min_len + n_chunks);
+                k_hash<<<(uint32_t)(ms / HASH_BLOCK) + 1, HASH_BLOCK, 0, c.st>>>(
+                    R.xf_kind, e->d_hash_key, e->d_hash_mid, c.text, c.offs, e->rsp, e->lane_sp + n_chunks, e->d_err, c.out);
             }
-            if (e->timing >= 1) HIPCHK(hipEventRecord(e->kev[3], st));
+            if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->kev[3], c.st));
             if (!wf)        // (window findings are not counted, as on the incremental window path)
-                k_hist_reduce<<<dim3(e->hist_types, std::max(1u, std::min(32u, nsb / 256))), 256, 0, st>>>(
+                k_hist_reduce<<<dim3(e->hist_types, std::max(1u, std::min(32u, nsb / 256))), 256, 0, c.st>>>(
                     e->hist_part, nsb, (int)e->hist_types, e->d_err, e->hist);
         }
         if (wf) {           // the new rows enter their rings; their context records are written
-            k_win_commit<<<(uint32_t)(((uint64_t)wf->n_new * 16 + 255) / 256), 256, 0, st>>>(wf->W, wf->Bnew, wf->wnew,
+            k_win_commit<<<(uint32_t)(((uint64_t)wf->n_new * 16 + 255) / 256), 256, 0, c.st>>>(wf->W, wf->Bnew, wf->wnew,
                                                                                              e->d_err);
-            k_ctx_commit<<<std::min<uint32_t>((wf->n_new + 255) / 256, 4 * e->n_cu), 256, 0, st>>>(
-                wf->slot_new, wf->kw_new, wf->ts_new, e->incl, e->ncommit, e->commit, e->d_err, e->st_group, e->st_ts);
+            launch_ctx_commit(e, wf->n_new, wf->slot_new, wf->kw_new, wf->ts_new, c.st);
         } else {
-            k_ctx_commit<<<std::min<uint32_t>((n_utt + 255) / 256, 4 * e->n_cu), 256, 0, st>>>(
-                slot, e->kw, ts, e->incl, e->ncommit, e->commit, e->d_err, e->st_group, e->st_ts);
+            launch_ctx_commit(e, c.n_utt, c.slot, e->kw, c.ts, c.st);
         }
         HIPCHK(hipGetLastError());
     }
-    if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[5], st));
-    HIPCHK(hipMemcpyAsync(e->h_totals, e->d_totals, hist_bytes(e), hipMemcpyDeviceToHost, st));
-    e->h_hist_valid = true;
-    HIPCHK(hipEventRecord(e->tev[6], st));
-    return PII_OK;
+    return end_call(e, c.st, hist_bytes(e), true);
 }
 
 int ensure_window_scratch(pii_engine* e, uint32_t n_utt) {
@@ -5707,32 +5579,22 @@ int ensure_window_scratch(pii_engine* e, uint32_t n_utt) {
     return PII_OK;
 }
 
-// the window history rings (pii_window_enable, pii_context_resize): persistent per-slot state, plain
-// allocations outside the work-buffer accounting; empty rings
-struct WinTables {
-    WDesc* desc = nullptr;
-    uint32_t *cnt = nullptr, *head = nullptr;
-    uint8_t* arena = nullptr;
-};
+void free_window_tables(WinTables& w) {
+    for (void* p : {(void*)w.desc, (void*)w.cnt, (void*)w.head, (void*)w.arena})
+        if (p) (void)hipFree(p);
+    w = WinTables{};
+}
+// empty rings for ns slots
 int alloc_window_tables(pii_engine* e, WinTables& w, size_t ns, uint32_t window_n, uint32_t slot_bytes) {
     const bool ok = hipMalloc(&w.desc, ns * window_n * sizeof(WDesc)) == hipSuccess &&
                     hipMalloc(&w.cnt, ns * 4) == hipSuccess && hipMalloc(&w.head, ns * 4) == hipSuccess &&
                     hipMalloc(&w.arena, ns * (size_t)slot_bytes) == hipSuccess &&
                     hipMemset(w.cnt, 0, ns * 4) == hipSuccess && hipMemset(w.head, 0, ns * 4) == hipSuccess;
     if (ok) return PII_OK;
-    for (void* p : {(void*)w.desc, (void*)w.cnt, (void*)w.head, (void*)w.arena})
-        if (p) (void)hipFree(p);
-    w = WinTables{};
+    free_window_tables(w);
     (void)hipGetLastError();
     e->err = "device allocation failed: the window history rings";
     return PII_E_NOMEM;
-}
-void free_window_tables(pii_engine* e) {
-    for (void* p : {(void*)e->wr_desc, (void*)e->wr_cnt, (void*)e->wr_head, (void*)e->wr_arena})
-        if (p) (void)hipFree(p);
-    e->wr_desc = nullptr;
-    e->wr_cnt = e->wr_head = nullptr;
-    e->wr_arena = nullptr;
 }
 
 int ensure_join(pii_engine* e, uint32_t n_utt) {
@@ -5756,44 +5618,31 @@ int ensure_join(pii_engine* e, uint32_t n_utt) {
 // the joined size; the windows are materialised; pass 2 is the ordinary pipeline over them as
 // CUSTOMER rows with the given context groups, then the new rows enter their rings and the context
 // records are written -- only when every stage succeeded.
-int run_window_full(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint32_t n_utt, uint64_t base,
-                    uint64_t total_bytes, const uint32_t* slot, const uint8_t* role, const int64_t* ts, uint8_t* out,
-                    uint64_t out_cap, uint64_t* out_offs, pii_span* spans, uint32_t span_cap, int16_t* win_ctx,
-                    hipStream_t st) {
-    e->lane_shift = pick_lane_shift(e, total_bytes);
-    e->r0 = (uint32_t)(((uintptr_t)text + base) & 63);
-    e->long_min = 2u << e->lane_shift;
-    const uint32_t n_chunks = lane_count(e, total_bytes);
-    e->last_lanes = n_chunks;
-    int rc = ensure_scratch(e, n_utt, total_bytes, n_chunks);
-    if (rc || (rc = ensure_queues(e, total_bytes)) || (rc = ensure_window_scratch(e, n_utt)) || (rc = ensure_join(e, n_utt)))
-        return rc;
-    e->last = pii_engine::Call{text, offs, n_utt, base, total_bytes, slot, role, ts, out, out_cap, out_offs, spans,
-                               span_cap, win_ctx, st, nullptr, nullptr, 0};
-    e->last_kind = 1;
-    e->last_gated = false;
-    int16_t* wctx = win_ctx ? win_ctx : e->wctx;
-    const unsigned long long* pcount =
-        n_chunks > 0 ? reinterpret_cast<const unsigned long long*>(e->lane_pair + n_chunks) : e->pair_count;
-    if ((rc = launch_front(e, text, offs, n_utt, n_chunks, base, total_bytes, slot, role, ts, e->ctx, wctx, pcount, st,
-                           true, nullptr, true, false)))
-        return rc;
-    const WinRing W{e->wr_desc, e->wr_cnt, e->wr_head, e->wr_arena, e->win_n, e->win_slot_bytes, e->n_slots, 0};
-    if (n_utt) HIPCHK(hipMemsetAsync(e->wc_n, 0, (size_t)n_utt * 4, st));      // text-only ring entries
-    const WinBatch B{text, offs, slot, e->wc, e->wc_first, e->wc_n, n_utt};
-    const uint32_t nb = (n_utt + 255) / 256;
-    if (n_utt) {
-        k_win_plan<<<nb, 256, 0, st>>>(W, B, e->wbound, e->wnew, e->d_err);
-        k_win_alloc<<<nb, 256, 0, st>>>(W, B, e->wnew, e->d_err);
-        k_win_jlen<<<nb, 256, 0, st>>>(W, B, e->jlen, e->d_err);
+int run_window_full(pii_engine* e, const Call& c) {
+    // pass 1 cuts rows like the main path, is not gated, and leaves kev_valid to pass 2
+    CallGeo cg;
+    const CallPlan plan{/*kind*/ 1, /*cut_lanes*/ 2, /*min_len*/ 0, ENS_QUEUES | ENS_WINDOW | ENS_JOIN, /*gated*/ F_CLEAR,
+                        /*kev*/ F_KEEP};
+    int rc = begin_call(e, c, plan, cg);
+    if (rc) return rc;
+    int16_t* wctx = c.ctx_info ? c.ctx_info : e->wctx;
+    if ((rc = launch_front(e, c, cg, {e->ctx, wctx, true, nullptr, true, false}))) return rc;
+    const WinRing W{e->wr.desc, e->wr.cnt, e->wr.head, e->wr.arena, e->win_n, e->win_slot_bytes, e->n_slots, 0};
+    if (c.n_utt) HIPCHK(hipMemsetAsync(e->wc_n, 0, (size_t)c.n_utt * 4, c.st));      // text-only ring entries
+    const WinBatch B{c.text, c.offs, c.slot, e->wc, e->wc_first, e->wc_n, c.n_utt};
+    const uint32_t nb = (c.n_utt + 255) / 256;
+    if (c.n_utt) {
+        k_win_plan<<<nb, 256, 0, c.st>>>(W, B, e->wbound, e->wnew, e->d_err);
+        k_win_alloc<<<nb, 256, 0, c.st>>>(W, B, e->wnew, e->d_err);
+        k_win_jlen<<<nb, 256, 0, c.st>>>(W, B, e->jlen, e->d_err);
     }
-    k_err_save<<<1, 1, 0, st>>>(e->d_err, e->err_saved);
+    k_err_save<<<1, 1, 0, c.st>>>(e->d_err, e->err_saved);
     HIPCHK(hipGetLastError());
-    if ((rc = exclusive_scan(e, e->jlen, n_utt, e->joff, st))) return rc;
-    HIPCHK(hipMemcpyAsync(e->h_jtotal, e->joff + n_utt, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if ((rc = exclusive_scan(e, e->jlen, c.n_utt, e->joff, c.st))) return rc;
+    HIPCHK(hipMemcpyAsync(e->h_jtotal, e->joff + c.n_utt, 8, hipMemcpyDeviceToHost, c.st));
+    HIPCHK(hipStreamSynchronize(c.st));
     const uint64_t jt = *e->h_jtotal;
-    if (jt > PII_MAX_BATCH_BYTES || jt + 2ull * n_utt + (jt >> MIN_LANE_SHIFT) > 0xFFFFFFF0ull) {
+    if (jt > PII_MAX_BATCH_BYTES || jt + 2ull * c.n_utt + (jt >> MIN_LANE_SHIFT) > 0xFFFFFFF0ull) {
         e->err = "the call's joined windows exceed PII_MAX_BATCH_BYTES; split the batch";
         return PII_E_ARG;
     }
@@ -5801,832 +5650,408 @@ int run_window_full(pii_engine* e, const uint8_t* text, const uint64_t* offs, ui
         if ((rc = grow(e, e->jbuf, jt + jt / 8 + 64))) return rc;
         e->cap_jbuf = jt + jt / 8 + 64;
     }
-    if (n_utt) k_win_join<<<(n_utt + 3) / 4, 256, 0, st>>>(W, B, e->joff, e->jbuf, e->d_err);
+    if (c.n_utt) k_win_join<<<(c.n_utt + 3) / 4, 256, 0, c.st>>>(W, B, e->joff, e->jbuf, e->d_err);
     HIPCHK(hipGetLastError());
     int32_t* kwA = e->kw;                // pass 2 must not overwrite the new rows' keyword groups
     e->kw = e->kw2;
-    const WinFull wf{wctx, e->err_saved, W, B, e->wnew, slot, ts, kwA, n_utt};
-    rc = run_pipeline(e, e->jbuf, e->joff, n_utt, 0, jt, slot, e->jrole, ts, out, out_cap, out_offs, spans, span_cap,
-                      nullptr, st, nullptr, nullptr, 0, &wf);
+    const WinFull wf{wctx, e->err_saved, W, B, e->wnew, c.slot, c.ts, kwA, c.n_utt};
+    Call j = c;                          // the joined windows as rows; e->last stays the call's own record
+    j.text = e->jbuf;
+    j.offs = e->joff;
+    j.base = 0;
+    j.total = jt;
+    j.role = e->jrole;
+    j.ctx_info = nullptr;
+    rc = run_pipeline(e, j, &wf);
     e->kw = kwA;
     return rc;
 }
 
 // the window re-scan call (a12): the shared front over the NEW rows only, then resident candidates,
 // window selection, window redaction, ring commit
-int run_window(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint32_t n_utt, uint64_t base,
-               uint64_t total_bytes, const uint32_t* slot, const uint8_t* role, const int64_t* ts, uint8_t* out, uint64_t out_cap,
-               uint64_t* out_offs, pii_span* spans, uint32_t span_cap, int16_t* win_ctx, hipStream_t st) {
+// (c.ctx_info: the rows' windows' context groups, win_ctx)
+int run_window(pii_engine* e, const Call& c) {
     if (e->win_n == 0) {
         e->err = "window re-scan not enabled (pii_window_enable)";
         return PII_E_ARG;
     }
-    if (total_bytes > PII_MAX_BATCH_BYTES || total_bytes + 2ull * n_utt + (total_bytes >> MIN_LANE_SHIFT) > 0xFFFFFFF0ull) {
-        e->err = "batch larger than PII_MAX_BATCH_BYTES (positions and event arenas are 32-bit); split it";
-        return PII_E_ARG;
-    }
-    if (e->win_full)
-        return run_window_full(e, text, offs, n_utt, base, total_bytes, slot, role, ts, out, out_cap, out_offs, spans,
-                               span_cap, win_ctx, st);
-    e->lane_shift = pick_lane_shift(e, total_bytes);
-    e->r0 = (uint32_t)(((uintptr_t)text + base) & 63);
+    if (e->win_full) return run_window_full(e, c);
     // rows whole by default; PII_WIN_LONG = n cuts rows longer than n lanes like the main path's long
     // rows (k_win_cands then walks a cut row whole).  A step's scan takes as long as its longest lane
     // (a whole 750-byte row of 128-byte lanes), and cutting at 2 lanes takes k_scan 67 -> 53 us, but
     // the stitching, the long-row list and the cut-row candidate walk cost more
-    e->long_min = e->win_long ? e->win_long << e->lane_shift : NO_CUTS;
-    const uint32_t n_chunks = lane_count(e, total_bytes);
-    e->last_lanes = n_chunks;
-    int rc = ensure_scratch(e, n_utt, total_bytes, n_chunks);
-    if (rc || (rc = ensure_queues(e, total_bytes)) || (rc = ensure_window_scratch(e, n_utt))) return rc;
-    e->last = pii_engine::Call{text, offs, n_utt, base, total_bytes, slot, role, ts, out, out_cap, out_offs, spans,
-                               span_cap, win_ctx, st};
-    e->last_kind = 1;
+    // (the incremental path has never touched last_gated: pii_last_stats reports the last gated call's)
+    CallGeo cg;
+    const CallPlan plan{/*kind*/ 1, /*cut_lanes*/ e->k.win_long, /*min_len*/ 0, ENS_QUEUES | ENS_WINDOW, /*gated*/ F_KEEP,
+                        /*kev*/ F_SET};
+    int rc = begin_call(e, c, plan, cg);
+    if (rc) return rc;
+    const uint32_t n_chunks = cg.n_chunks;
+    const unsigned long long* pcount = cg.pcount;
     const RulesDev& R = e->R;
-    int16_t* wctx = win_ctx ? win_ctx : e->wctx;
-    e->kev_valid = n_utt > 0 && total_bytes > 0;
-    const unsigned long long* pcount =
-        n_chunks > 0 ? reinterpret_cast<const unsigned long long*>(e->lane_pair + n_chunks) : e->pair_count;
-    if ((rc = launch_front(e, text, offs, n_utt, n_chunks, base, total_bytes, slot, role, ts, e->ctx, wctx, pcount,
-                           st, true)))
-        return rc;
-    if (n_utt > 0 && n_chunks > 0) {
-        (e->img_eval.global ? k_win_eval<true> : k_win_eval<false>)<<<e->n_seg, PAIR_BLOCK, e->img_eval.lds(), st>>>(
-            e->img_eval.d, e->img_eval.li, text, offs, pcount, e->pair_cap, e->matched, e->mcount, e->n_seg,
+    int16_t* wctx = c.ctx_info ? c.ctx_info : e->wctx;
+    if ((rc = launch_front(e, c, cg, {e->ctx, wctx, true}))) return rc;
+    if (c.n_utt > 0 && n_chunks > 0) {
+        (e->img_eval.global ? k_win_eval<true> : k_win_eval<false>)<<<e->n_seg, PAIR_BLOCK, e->img_eval.lds(), c.st>>>(
+            e->img_eval.d, e->img_eval.li, c.text, c.offs, pcount, e->pair_cap, e->matched, e->mcount, e->n_seg,
             e->evloc, e->pend, e->pres, e->phot);
-        k_win_cands<<<(n_chunks + 255) / 256, 256, 0, st>>>(make_geo(e, offs, n_utt, n_chunks, base), e->lane_pair, e->lane_np, e->evloc, e->pres,
+        k_win_cands<<<(n_chunks + 255) / 256, 256, 0, c.st>>>(cg.g, e->lane_pair, e->lane_np, e->evloc, e->pres,
                                                             e->pend, e->phot, e->pair_cap, e->spill, e->wc, e->wc_first,
                                                             e->wc_n, e->d_err);
         HIPCHK(hipGetLastError());
     }
-    const WinRing W{e->wr_desc, e->wr_cnt, e->wr_head, e->wr_arena, e->win_n, e->win_slot_bytes, e->n_slots, 0};
-    const WinBatch B{text, offs, slot, e->wc, e->wc_first, e->wc_n, n_utt};
-    const uint32_t nb = (n_utt + 255) / 256;
-    if (n_utt > 0 && n_chunks > 0 && R.n_hot > 0) {
+    const WinRing W{e->wr.desc, e->wr.cnt, e->wr.head, e->wr.arena, e->win_n, e->win_slot_bytes, e->n_slots, 0};
+    const WinBatch B{c.text, c.offs, c.slot, e->wc, e->wc_first, e->wc_n, c.n_utt};
+    const uint32_t nb = (c.n_utt + 255) / 256;
+    if (c.n_utt > 0 && n_chunks > 0 && R.n_hot > 0) {
         // (the image in LDS when it fits beside the halo tables, else read in place)
         const bool hg = e->img_eval.global || ((size_t)e->img_eval.li.total + 15) / 16 * 16 + HALO_LDS > IMG_LDS_MAX;
         const size_t hl = (hg ? 0 : ((size_t)e->img_eval.li.total + 15) / 16 * 16) + HALO_LDS;
-        (hg ? k_win_halo<true> : k_win_halo<false>)<<<(n_utt + HALO_ROWS - 1) / HALO_ROWS, HALO_ROWS, hl, st>>>(
-            e->img_eval.d, e->img_eval.li, W, B, e->wc, e->halo_items, e->d_err);
+        (hg ? k_win_halo<true> : k_win_halo<false>)<<<(c.n_utt + HALO_ROWS - 1) / HALO_ROWS, HALO_ROWS, hl, c.st>>>(
+            e->img_eval.d, e->img_eval.li, W, B, e->wc, e->k.halo_items, e->d_err);
     }
-    if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[3], st));
-    if (n_utt > 0) {
-        k_win_plan<<<nb, 256, 0, st>>>(W, B, e->wbound, e->wnew, e->d_err);
-        if ((rc = exclusive_scan(e, e->wbound, n_utt, e->wfbase, st))) return rc;
-        (e->img_wsel.global ? k_win_select<true> : k_win_select<false>)<<<nb, 256, e->img_wsel.lds(), st>>>(
+    if (e->k.timing >= 2) HIPCHK(hipEventRecord(e->tev[3], c.st));
+    if (c.n_utt > 0) {
+        k_win_plan<<<nb, 256, 0, c.st>>>(W, B, e->wbound, e->wnew, e->d_err);
+        if ((rc = exclusive_scan(e, e->wbound, c.n_utt, e->wfbase, c.st))) return rc;
+        (e->img_wsel.global ? k_win_select<true> : k_win_select<false>)<<<nb, 256, e->img_wsel.lds(), c.st>>>(
             R, e->img_wsel.d, e->img_wsel.li, W, B, wctx, e->wfbase,
                                                              e->wfd_cap, e->wfd, e->n_wfind, e->wout_len, e->d_err);
         HIPCHK(hipGetLastError());
     }
-    if (n_utt > 0) {
-        if ((rc = exclusive_scan(e, e->wout_len, n_utt, out_offs, st, e->n_wfind, n_utt, e->wspan_offs))) return rc;
+    if (c.n_utt > 0) {
+        if ((rc = exclusive_scan(e, e->wout_len, c.n_utt, c.out_offs, c.st, e->n_wfind, c.n_utt, e->wspan_offs))) return rc;
     } else {
-        if ((rc = exclusive_scan(e, e->wout_len, n_utt, out_offs, st))) return rc;
-        if ((rc = exclusive_scan(e, e->n_wfind, n_utt, e->wspan_offs, st))) return rc;
+        if ((rc = exclusive_scan(e, e->wout_len, c.n_utt, c.out_offs, c.st))) return rc;
+        if ((rc = exclusive_scan(e, e->n_wfind, c.n_utt, e->wspan_offs, c.st))) return rc;
     }
-    if (n_utt > 0) k_win_alloc<<<nb, 256, 0, st>>>(W, B, e->wnew, e->d_err);
-    k_finalize<<<1, 1, 0, st>>>(out_offs, e->wspan_offs, n_utt, n_utt, out_cap, span_cap, e->d_err, e->d_totals,
-                                pcount, n_chunks > 0 ? e->lane_ev + n_chunks : nullptr, n_utt > 0 ? e->wfbase + n_utt : nullptr,
+    if (c.n_utt > 0) k_win_alloc<<<nb, 256, 0, c.st>>>(W, B, e->wnew, e->d_err);
+    k_finalize<<<1, 1, 0, c.st>>>(c.out_offs, e->wspan_offs, c.n_utt, c.n_utt, c.out_cap, c.span_cap, e->d_err, e->d_totals,
+                                pcount, n_chunks > 0 ? e->lane_ev + n_chunks : nullptr, c.n_utt > 0 ? e->wfbase + c.n_utt : nullptr,
                                 nullptr);
     HIPCHK(hipGetLastError());
-    if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[4], st));
-    if (n_utt > 0) {
-        if (e->timing >= 1) HIPCHK(hipEventRecord(e->kev[2], st));
-        k_win_redact<<<(n_utt + WIN_TILE - 1) / WIN_TILE, REDACT_BLOCK, 0, st>>>(
-            R, W, B, e->wfd, e->wfbase, e->n_wfind, out_offs, e->wspan_offs, e->d_err, out, spans);
-        if (e->timing >= 1) HIPCHK(hipEventRecord(e->kev[3], st));
-        k_win_commit<<<(uint32_t)(((uint64_t)n_utt * 16 + 255) / 256), 256, 0, st>>>(W, B, e->wnew, e->d_err);
-        k_ctx_commit<<<std::min<uint32_t>(nb, 4 * e->n_cu), 256, 0, st>>>(slot, e->kw, ts, e->incl, e->ncommit,
-                                                                          e->commit, e->d_err, e->st_group, e->st_ts);
+    if (e->k.timing >= 2) HIPCHK(hipEventRecord(e->tev[4], c.st));
+    if (c.n_utt > 0) {
+        if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->kev[2], c.st));
+        k_win_redact<<<(c.n_utt + WIN_TILE - 1) / WIN_TILE, REDACT_BLOCK, 0, c.st>>>(
+            R, W, B, e->wfd, e->wfbase, e->n_wfind, c.out_offs, e->wspan_offs, e->d_err, c.out, c.spans);
+        if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->kev[3], c.st));
+        k_win_commit<<<(uint32_t)(((uint64_t)c.n_utt * 16 + 255) / 256), 256, 0, c.st>>>(W, B, e->wnew, e->d_err);
+        launch_ctx_commit(e, c.n_utt, c.slot, e->kw, c.ts, c.st);
         HIPCHK(hipGetLastError());
     }
-    if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[5], st));
-    HIPCHK(hipMemcpyAsync(e->h_totals, e->d_totals, hist_bytes(e), hipMemcpyDeviceToHost, st));
-    e->h_hist_valid = true;
-    HIPCHK(hipEventRecord(e->tev[6], st));
-    return PII_OK;
+    return end_call(e, c.st, hist_bytes(e), true);
 }
 
 // pii_context_update: the shared front without the pair queue or FIRST runs (the count pass yields the
 // AGENT rows' keyword groups), the context kernels and the context commit
-int run_context(pii_engine* e, const uint8_t* text, const uint64_t* offs, uint32_t n_utt, uint64_t total_bytes,
-                const uint32_t* slot, const uint8_t* role, const int64_t* ts, int16_t* ctx_info, hipStream_t st) {
-    if (total_bytes > PII_MAX_BATCH_BYTES || total_bytes + 2ull * n_utt + (total_bytes >> MIN_LANE_SHIFT) > 0xFFFFFFF0ull) {
-        e->err = "batch larger than PII_MAX_BATCH_BYTES (positions and event arenas are 32-bit); split it";
-        return PII_E_ARG;
-    }
-    e->lane_shift = pick_lane_shift(e, total_bytes);
-    e->r0 = (uint32_t)((uintptr_t)text & 63);
-    e->long_min = 2u << e->lane_shift;
-    const uint32_t n_chunks = lane_count(e, total_bytes);
-    e->last_lanes = n_chunks;
-    int rc = ensure_scratch(e, n_utt, total_bytes, n_chunks);
+// (the record of a context-only call has base 0 and no output side; only the 64 bytes of totals come
+// back, so the pinned histogram copy goes stale)
+int run_context(pii_engine* e, const Call& c) {
+    CallGeo cg;
+    const CallPlan plan{/*kind*/ 2, /*cut_lanes*/ 2, /*min_len*/ 0, /*ensure*/ 0, /*gated*/ F_CLEAR, /*kev*/ F_CLEAR};
+    int rc = begin_call(e, c, plan, cg);
     if (rc) return rc;
-    e->last = pii_engine::Call{text, offs, n_utt, 0, total_bytes, slot, role, ts, nullptr, 0, nullptr, nullptr,
-                               0, ctx_info, st, nullptr, nullptr, 0};
-    e->last_kind = 2;
-    e->last_gated = false;
-    e->kev_valid = false;
-    const unsigned long long* pcount =
-        n_chunks > 0 ? reinterpret_cast<const unsigned long long*>(e->lane_pair + n_chunks) : e->pair_count;
-    if ((rc = launch_front(e, text, offs, n_utt, n_chunks, 0, total_bytes, slot, role, ts, ctx_info, nullptr, pcount,
-                           st, true, nullptr, true, false)))
-        return rc;
-    if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[3], st));
-    k_ctx_totals<<<1, 1, 0, st>>>(e->d_err, e->d_totals);
-    if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[4], st));
-    if (n_utt > 0)
-        k_ctx_commit<<<std::min<uint32_t>((n_utt + 255) / 256, 4 * e->n_cu), 256, 0, st>>>(
-            slot, e->kw, ts, e->incl, e->ncommit, e->commit, e->d_err, e->st_group, e->st_ts);
+    if ((rc = launch_front(e, c, cg, {c.ctx_info, nullptr, true, nullptr, true, false}))) return rc;
+    if (e->k.timing >= 2) HIPCHK(hipEventRecord(e->tev[3], c.st));
+    k_ctx_totals<<<1, 1, 0, c.st>>>(e->d_err, e->d_totals);
+    if (e->k.timing >= 2) HIPCHK(hipEventRecord(e->tev[4], c.st));
+    if (c.n_utt > 0) launch_ctx_commit(e, c.n_utt, c.slot, e->kw, c.ts, c.st);
     HIPCHK(hipGetLastError());
-    if (e->timing >= 2) HIPCHK(hipEventRecord(e->tev[5], st));
-    HIPCHK(hipMemcpyAsync(e->h_totals, e->d_totals, 64, hipMemcpyDeviceToHost, st));
-    e->h_hist_valid = false;
-    HIPCHK(hipEventRecord(e->tev[6], st));
-    return PII_OK;
+    return end_call(e, c.st, 64, false);
 }
 
 int rerun_last(pii_engine* e) {
-    const pii_engine::Call c = e->last;
-    if (e->last_kind == 2)
-        return run_context(e, c.text, c.offs, c.n_utt, c.total, c.slot, c.role, c.ts, c.ctx_info, c.st);
-    if (e->last_kind == 1)
-        return run_window(e, c.text, c.offs, c.n_utt, c.base, c.total, c.slot, c.role, c.ts, c.out, c.out_cap,
-                          c.out_offs, c.spans, c.span_cap, c.ctx_info, c.st);
-    return run_pipeline(e, c.text, c.offs, c.n_utt, c.base, c.total, c.slot, c.role, c.ts, c.out, c.out_cap,
-                        c.out_offs, c.spans, c.span_cap, c.ctx_info, c.st, c.ext, c.ext_n, c.ext_stride);
+    const Call c = e->last;
+    return e->last_kind == 2 ? run_context(e, c) : e->last_kind == 1 ? run_window(e, c) : run_pipeline(e, c);
 }
 
-struct ExtArgs {
-    const pii_span* ext;
-    const uint32_t* ext_n;
-    uint32_t stride;
-};
-int device_call(pii_engine* e, bool window, const uint8_t* d_bytes, const uint64_t* d_offsets, uint32_t n_utt,
-                const uint32_t* d_slot, const uint8_t* d_role, const int64_t* d_ts, uint8_t* d_out, uint64_t out_cap,
-                uint64_t* d_out_offsets, pii_span* d_spans, uint32_t span_cap, int16_t* d_ctx_info, void* stream,
-                const uint64_t* declared, const ExtArgs* x = nullptr);
+// The extern "C" functions name their arguments once, into a record: the rows, then the output side.
+Call call_rows(const uint8_t* bytes, const uint64_t* offsets, uint32_t n_utt, const uint32_t* slot, const uint8_t* role,
+               const int64_t* ts) {
+    Call c{};
+    c.text = bytes;
+    c.offs = offsets;
+    c.n_utt = n_utt;
+    c.slot = slot;
+    c.role = role;
+    c.ts = ts;
+    return c;
+}
+Call& with_out(Call& c, uint8_t* out, uint64_t out_cap, uint64_t* out_offs, pii_span* spans, uint32_t span_cap,
+               int16_t* ctx_info) {
+    c.out = out;
+    c.out_cap = out_cap;
+    c.out_offs = out_offs;
+    c.spans = spans;
+    c.span_cap = span_cap;
+    c.ctx_info = ctx_info;
+    return c;
+}
+Call& with_ext(Call& c, const pii_span* ext, const uint32_t* ext_n, uint32_t ext_stride) {
+    c.ext = ext;
+    c.ext_n = ext_n;
+    c.ext_stride = ext_stride;
+    return c;
+}
+int device_call(pii_engine* e, bool window, Call c, void* stream, const uint64_t* declared);
+int host_call(pii_engine* e, bool window, const Call& h, uint32_t* n_spans);
+int host_context(pii_engine* e, const Call& h);
+// ------------------------------------------------------------------------------- engine creation
+EngineKnobs read_knobs() {
+    constexpr int ANY = 0x7fffffff;
+    auto env = [](const char* name, int def, int lo, int hi) {
+        const char* v = std::getenv(name);
+        return v ? std::max(lo, std::min(hi, std::atoi(v))) : def;
+    };
+    EngineKnobs k;
+    k.rules.first_drop = env("PII_FIRST_DROP", 1, -ANY, ANY) != 0;
+    k.rules.first_hot_big = (size_t)env("PII_FIRST_HOT_BIG", (int)FIRST_HOT_BIG, 0, ANY);
+    k.rules.first_hot_lds = (size_t)env("PII_FIRST_HOT_LDS", (int)FIRST_HOT_LDS, 0, 158 * 1024);
+    k.rules.first_hot = (uint32_t)env("PII_FIRST_HOT", ANY, 0, ANY);
+    k.verbose = env("PII_VERBOSE", 0, -ANY, ANY) > 0;
+    k.eval_split = (uint32_t)env("PII_EVAL_SPLIT", 0, 1, 64);
+    k.merge_cap = (uint32_t)env("PII_MERGE_CAP", MERGE_EVW, 0, MERGE_EVW);
+    k.scan_count = env("PII_SCAN_COUNT", 1, -ANY, ANY) != 0;
+    k.long_gate = env("PII_LONG_GATE", 1, -ANY, ANY) != 0;
+    k.scan_ilv = env("PII_SCAN_ILV", 1, -ANY, ANY) != 0;
+    k.win_long = (uint32_t)env("PII_WIN_LONG", 0, 0, 64);
+    k.halo_items = (uint32_t)env("PII_HALO_ITEMS", HALO_ITEMS, 0, HALO_ITEMS);
+    k.timing = env("PII_TIMING", 1, 0, 2);
+    k.scan_streams = (uint32_t)env("PII_SCAN_STREAMS", SCAN_STREAMS, 1, 3);
+    return k;
+}
+
+bool upload(const void* src, size_t bytes, void** dst) {
+    return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+}
+bool upload_image(const HostImage& h, DevImage& d) {
+    if (h.bytes.empty()) return true;
+    d.li = h.li;
+    d.global = h.global;
+    return upload(h.bytes.data(), h.bytes.size(), reinterpret_cast<void**>(&d.d));
+}
+
+// the rules buffer, the SCAN groups' records and the images into device memory; the table pointers
+bool upload_rules(pii_engine* e, HostRules& H) {
+    if (!upload(H.packed.data(), H.packed.size(), &e->d_rules)) return false;
+    const uint8_t* b = static_cast<const uint8_t*>(e->d_rules);
+    auto set = [&](auto*& p, size_t off) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(b + off); };
+    RulesDev& R = e->R = H.R;
+    set(R.cmap4, H.off[TB_CMAP4]);
+    set(R.td, H.off[TB_TD]);
+    set(R.tk, H.off[TB_TK]);
+    set(R.d_accid, H.off[TB_D_ACCID]);
+    set(R.d_acc_off, H.off[TB_D_ACC_OFF]);
+    set(R.d_acc_ids, H.off[TB_D_ACC_IDS]);
+    set(R.k_accid, H.off[TB_K_ACCID]);
+    set(R.k_acc_min, H.off[TB_K_ACC_MIN]);
+    set(R.d_npair, H.off[TB_D_NPAIR]);
+    set(R.k_grp, H.off[TB_K_GRP]);
+    set(R.d_na, H.off[TB_D_NA]);
+    set(R.det_type, H.off[TB_DET_TYPE]);
+    set(R.det_val, H.off[TB_DET_VAL]);
+    set(R.det_lik, H.off[TB_DET_LIK]);
+    set(R.det_exidx, H.off[TB_DET_EXIDX]);
+    set(R.first_desc, H.off[TB_FIRST_DESC]);
+    set(R.hot_rule, H.off[TB_HOT_RULE]);
+    set(R.hot_desc, H.off[TB_HOT_DESC]);
+    set(R.var_enabled, H.off[TB_VAR_ENABLED]);
+    set(R.var_minlik, H.off[TB_VAR_MINLIK]);
+    set(R.rule_off, H.off[TB_RULE_OFF]);
+    set(R.rule_ids, H.off[TB_RULE_IDS]);
+    set(R.excl_off, H.off[TB_EXCL_OFF]);
+    set(R.excl_ids, H.off[TB_EXCL_IDS]);
+    set(R.tok_off, H.off[TB_TOK_OFF]);
+    set(R.tok_bytes, H.off[TB_TOK_BYTES]);
+    set(R.tok_len, H.off[TB_TOK_LEN]);
+    set(R.xf_kind, H.off[TB_XF_KIND]);
+    set(R.xf_mask, H.off[TB_XF_MASK]);
+    if (H.xf_hash) {
+        set(e->d_hash_key, H.off[TB_HASH_KEY]);
+        set(e->d_hash_mid, H.off[TB_HASH_MID]);
+    }
+    // SCAN groups: sg[0] = R; a group >= 1 has its own D tables and a 1-row K stub
+    e->scan_lds = H.scan_lds;
+    e->n_sg = 1 + (uint32_t)H.groups.size();
+    e->sg.assign(1, R);
+    e->sg_lds.assign(1, e->scan_lds);
+    for (const HostGroup& h : H.groups) {
+        RulesDev Rq = R;
+        set(Rq.cmap4, h.off[GT_CMAP4]);
+        set(Rq.td, h.off[GT_TD]);
+        set(Rq.tk, h.off[GT_TK]);
+        set(Rq.d_accid, h.off[GT_D_ACCID]);
+        set(Rq.k_accid, h.off[GT_K_ACCID]);
+        set(Rq.d_npair, h.off[GT_D_NPAIR]);
+        Rq.SD = h.SD;
+        Rq.CD = h.CD;
+        Rq.CDs = h.CDs;
+        Rq.dsh = h.dsh;
+        Rq.d_start = Rq.k_start = 0;
+        Rq.SK = 1;
+        Rq.CK = Rq.CKs = 2;
+        e->sg.push_back(Rq);
+        e->sg_lds.push_back(h.lds);
+    }
+    for (size_t q = 0; q < e->sg.size(); ++q) {
+        e->acct.accid[q] = e->sg[q].d_accid;
+        e->acct.npair[q] = e->sg[q].d_npair;
+    }
+    e->max_sg_lds = *std::max_element(e->sg_lds.begin(), e->sg_lds.end());
+    const std::vector<uint32_t> lds32(e->sg_lds.begin(), e->sg_lds.end());
+    if (!upload(e->sg.data(), e->sg.size() * sizeof(RulesDev), reinterpret_cast<void**>(&e->d_sg)) ||
+        !upload(lds32.data(), lds32.size() * 4, reinterpret_cast<void**>(&e->d_sg_lds)))
+        return false;
+    const std::pair<const char*, std::pair<const HostImage*, DevImage*>> ims[] = {
+        {"first", {&H.img_first, &e->img_first}},   {"first_hot", {&H.img_first_hot, &e->img_first_hot}},
+        {"eval", {&H.img_eval, &e->img_eval}},      {"eval_rg", {&H.img_eval_rg, &e->img_eval_rg}},
+        {"sel", {&H.img_sel, &e->img_sel}},         {"sel_rg", {&H.img_sel_rg, &e->img_sel_rg}},
+        {"wsel", {&H.img_wsel, &e->img_wsel}}};
+    for (auto& im : ims) {
+        if (!upload_image(*im.second.first, *im.second.second)) return false;
+        if (e->k.verbose && im.second.second->d)
+            std::fprintf(stderr, "pii: image %-9s %8u bytes %s\n", im.first, im.second.second->li.total,
+                         im.second.second->global ? "global" : "lds");
+    }
+    e->first_p_hot = H.first_p_hot;
+    e->lists_cl = H.lists_cl;
+    e->names = std::move(H.names);
+    e->kw_type = std::move(H.kw_type);
+    e->xf_kind = std::move(H.xf_kind);
+    e->xf_src = H.xf_src;
+    e->xf_mask = H.xf_mask;
+    e->xf_hash = H.xf_hash;
+    e->window_ok = H.window_ok;
+    return true;
+}
+
+// every kernel whose dynamic LDS (an image, the SCAN tables) passes the 64 KiB default
+bool raise_lds_limits(pii_engine* e) {
+    auto raise = [](const void* k, size_t bytes) {
+        return bytes <= 64 * 1024 ||
+               hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+    };
+    if (!raise((const void*)k_pair_first<true>, e->img_first_hot.li.total)) return false;
+    // (the list-less evaluation image is dropped where its kernel cannot take it)
+    if (e->img_eval_rg.d && !raise((const void*)k_pair_eval<false, true>, e->img_eval_rg.li.total)) {
+        (void)hipFree(e->img_eval_rg.d);
+        e->img_eval_rg = DevImage{};
+    }
+    // (the window re-scan's kernels read an image past LDS in place, like the pair kernels)
+    const std::pair<const void*, const DevImage*> big[] = {
+        {(const void*)k_pair_first<false>, &e->img_first}, {(const void*)k_pair_eval<false>, &e->img_eval},
+        {(const void*)k_select<false, false>, &e->img_sel}, {(const void*)k_sel_fix<false, false>, &e->img_sel},
+        {(const void*)k_select<false, true>, &e->img_sel}, {(const void*)k_sel_fix<false, true>, &e->img_sel},
+        {(const void*)k_select<false, false, true>, &e->img_sel},
+        {(const void*)k_sel_fix<false, false, true>, &e->img_sel},
+        {(const void*)k_select<false, true, true>, &e->img_sel}, {(const void*)k_sel_fix<false, true, true>, &e->img_sel},
+        {(const void*)k_pair_eval<false, false, true>, &e->img_eval},
+        {(const void*)k_win_eval<false>, &e->img_eval},
+        {(const void*)k_win_select<false>, &e->img_wsel}};
+    // k_win_halo<false>: its image plus HALO_LDS of tables (the launch falls back to <true> past the LDS)
+    if (!raise((const void*)k_win_halo<false>, IMG_LDS_MAX)) return false;
+    for (auto& kb : big)
+        if (!kb.second->global && !raise(kb.first, kb.second->li.total)) return false;
+    const size_t max_lds = e->max_sg_lds;
+    return raise((const void*)k_scan<true>, max_lds) && raise((const void*)k_scan<false>, max_lds) &&
+           raise((const void*)k_scan<false, SCAN_BLOCK_WIDE>, max_lds) && raise((const void*)k_scan_fix, max_lds + FIX_LDS);
+}
+
+// streams, events, the per-slot state, the counter block, the totals and their pinned copy
+bool alloc_state(pii_engine* e) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, e->device) == hipSuccess && prop.multiProcessorCount > 0)
+        e->n_cu = prop.multiProcessorCount;
+    // k_pair_first: two 1024-thread workgroups per CU, one round (2 or 4 rounds: 160 -> 165 / 164 µs,
+    // and k_pair_eval slower on the smaller segments)
+    e->n_seg = 2 * (uint32_t)e->n_cu;
+    if (hipMalloc(&e->mcount, e->n_seg * PAIR_WAVES * sizeof(uint32_t)) != hipSuccess) return false;
+    e->hist_types = (uint32_t)std::min(e->R.T, 1024);
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) return false;
+    e->own_stream = true;
+    if (e->n_sg > 1) {
+        e->n_aux = e->k.scan_streams - 1;
+        if (e->n_aux && hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess) return false;
+        for (uint32_t i = 0; i < e->n_aux; ++i)
+            if (hipStreamCreateWithFlags(&e->aux[i], hipStreamNonBlocking) != hipSuccess ||
+                hipEventCreateWithFlags(&e->ev_join[i], hipEventDisableTiming) != hipSuccess)
+                return false;
+    }
+    for (auto& t : e->kev)
+        if (hipEventCreate(&t) != hipSuccess) return false;
+    for (auto& t : e->tev)
+        if (hipEventCreate(&t) != hipSuccess) return false;
+    const size_t ns = std::max<uint32_t>(1, e->n_slots);
+    if (hipMalloc(&e->st_group, ns * 4) != hipSuccess || hipMalloc(&e->st_ts, ns * 8) != hipSuccess ||
+        hipMalloc(&e->stamp, ns * 4) != hipSuccess ||
+        hipMalloc(&e->d_err, 64) != hipSuccess || hipMalloc(&e->d_totals, hist_bytes(e)) != hipSuccess ||
+        hipMalloc(&e->lb_ticket, 32) != hipSuccess ||
+        hipMemset(e->lb_ticket, 0, 32) != hipSuccess)
+        return false;
+    e->long_count = e->d_err + 1;
+    e->ncommit = e->d_err + 2;
+    e->pair_count = reinterpret_cast<unsigned long long*>(e->d_err + 4);
+    // the histogram lives right after the totals, so one async copy at the end of a call brings both
+    e->hist = reinterpret_cast<unsigned long long*>(e->d_totals + 8);
+    if (hipHostMalloc(&e->h_totals, hist_bytes(e)) != hipSuccess) return false;
+    const std::vector<int32_t> g(ns, -1);
+    if (hipMemcpy(e->st_group, g.data(), ns * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(e->st_ts, 0, ns * 8) != hipSuccess || hipMemset(e->stamp, 0, ns * 4) != hipSuccess ||
+        hipMemset(e->hist, 0, std::max(e->R.T, 256) * 8) != hipSuccess)
+        return false;
+    k_noop<<<1, 64, 0, e->stream>>>();
+    return hipStreamSynchronize(e->stream) == hipSuccess;
+}
 }  // namespace
 
 extern "C" {
 
 const char* pii_last_error(pii_engine* e) { return e ? e->err.c_str() : "null engine"; }
 
+// Everything that can be wrong with the blob is found before the first HIP call (build_host_rules), so
+// a malformed blob is PII_E_RULES whether or not the device is usable.
 int pii_engine_create(const void* blob, size_t n, int device, uint32_t n_conv_slots, int64_t ttl_us,
                       pii_engine** out) {
     if (!blob || !out) return PII_E_ARG;
     *out = nullptr;
-    std::vector<Section> secs;
-    if (!parse_blob(static_cast<const uint8_t*>(blob), n, secs)) return PII_E_RULES;
-    auto find = [&](const char* nm) -> const Section* {
-        for (auto& s : secs)
-            if (s.name == nm) return &s;
-        return nullptr;
-    };
-    static const char* req[] = {"meta", "scan.cmap2", "scan.d.trans", "scan.d.accid", "scan.d.acc_off",
-                                "scan.d.acc_ids", "scan.k.trans", "scan.k.accid", "scan.k.acc_off", "scan.k.acc_ids",
-                                "det.type", "det.validator", "det.lik", "det.exidx", "det.first_desc", "hot.rule",
-                                "hot.dfa_desc", "pool.trans", "pool.flags", "pool.cmap", "var.enabled",
-                                "var.minlik", "var.rule_off", "var.rule_ids", "var.excl_off", "var.excl_ids",
-                                "kw.type", "kw.always", "types.names"};
-    for (auto r : req)
-        if (!find(r)) return PII_E_RULES;
-    const int64_t* meta = reinterpret_cast<const int64_t*>(find("meta")->data);
+    const EngineKnobs k = read_knobs();
+    HostRules H;
+    if (build_host_rules(static_cast<const uint8_t*>(blob), n, k.rules, H)) return PII_E_RULES;
     pii_engine* e = new pii_engine();
     e->device = device;
     e->n_slots = n_conv_slots;
     e->ttl_us = ttl_us;
-    RulesDev& R = e->R;
-    R.P = (int)meta[0];
-    R.G = (int)meta[1];
-    R.T = (int)meta[2];
-    R.V = (int)meta[3];
-    R.SD = (int)meta[4];
-    R.CD = (int)meta[5];
-    R.d_start = (int)meta[6];
-    R.SK = (int)meta[7];
-    R.CK = (int)meta[8];
-    R.k_start = (int)meta[9];
-    R.n_hot = (int)meta[10];
-    R.min_len = (int)std::max<int64_t>(1, meta[11]);
-    e->window_ok = meta[13] != 0;
-    auto fail = [&](const char* why) {
-        e->err = why;
+    // k_pair_eval work units per k_pair_first workgroup: 2 (config 2: 1 / 2 / 3 / 4 -> 342 / 312 / 315
+    // / 318 us); 4 for a large rule set (config 5's longer evaluations: 2 -> 4: 909 -> 893 us)
+    e->k = k;
+    if (!k.eval_split) e->k.eval_split = (size_t)H.R.V * H.R.T > LIST_DEDUP_KEYS ? 4 : 2;
+    int rc = PII_OK;
+    if (hipSetDevice(device) != hipSuccess) {
+        e->err = "hipSetDevice failed";
+        rc = PII_E_DEVICE;
+    } else if (!upload_rules(e, H) || !raise_lds_limits(e) || !alloc_state(e)) {
+        rc = PII_E_RULES;
+    }
+    if (rc) {
         pii_engine_destroy(e);
-        return PII_E_RULES;
-    };
-    if (R.P > 65535) return fail("too many detector patterns");
-    // scan table entries are 16-bit LDS byte addresses (k_scan layout: class map, D rows, K rows);
-    // rows are padded to an even class count so every row address is a multiple of 4 and bit 1 of
-    // an entry is free for the destination's end-of-text accept
-    R.CDs = (R.CD + 1) & ~1;
-    R.CKs = (R.CK + 1) & ~1;
-    R.dsh = 0;
-    const uint32_t td_words = (uint32_t)(R.SD * R.CDs / 2), tk_words = (uint32_t)(R.SK * R.CKs / 2);
-    const uint32_t tk_base = SCAN_TD_BASE + td_words * 4;
-    if ((uint64_t)tk_base + (uint64_t)tk_words * 4 > 65536) return fail("SCAN tables exceed 64 KiB of LDS");
-    if (R.T > 65535) return fail("too many types");
-    // names + tokens
-    {
-        const Section* s = find("types.names");
-        const char* p = reinterpret_cast<const char*>(s->data);
-        size_t i = 0;
-        while (i < s->bytes) {
-            size_t l = strnlen(p + i, s->bytes - i);
-            e->names.emplace_back(p + i, l);
-            i += l + 1;
-        }
-        if ((int)e->names.size() != R.T) return fail("type table mismatch");
+        return rc;
     }
-    {
-        const Section* s = find("kw.type");
-        const uint16_t* k = reinterpret_cast<const uint16_t*>(s->data);
-        for (int g = 0; g < R.G; ++g) e->kw_type.push_back(k[g]);
-    }
-    // host-side derived tables
-    std::vector<uint16_t> td(R.SD * R.CDs, 0), tk(R.SK * R.CKs, 0), dacc(R.SD * R.CDs, 0), kacc(R.SK * R.CKs, 0);
-    // entry (row, class) = address of the destination row | accept | accept of the destination's
-    // end-of-text transition (class C-1) << 1, so k_scan resets at an utterance start without
-    // reading the end-of-text entry
-    // (k_scan: rows are placed with the START state first -- row = pos(state) -- and entries are the
-    // destination row's byte offset from the table base, so a reset is "row 0"; the class words carry
-    // the table bases; accept-id tables follow the same placement)
-    auto relayout = [](const uint16_t* s, const uint16_t* acc, int S, int C, int Cs, int start, uint16_t* t,
-                       uint16_t* a, int dsh = 0) {
-        auto pos = [start](uint32_t r) { return r == (uint32_t)start ? 0u : r == 0 ? (uint32_t)start : r; };
-        for (int r = 0; r < S; ++r)
-            for (int c = 0; c < C; ++c) {
-                const uint32_t v = s[r * C + c], dst = v & 0x7fff;
-                const uint32_t eot = s[dst * C + C - 1] >> 15;
-                t[pos(r) * Cs + c] = (uint16_t)(((pos(dst) * Cs * 2) >> dsh) | (v >> 15) | (eot << 1));
-                a[pos(r) * Cs + c] = acc[r * C + c];
-            }
-    };
-    {
-        relayout(reinterpret_cast<const uint16_t*>(find("scan.d.trans")->data),
-                 reinterpret_cast<const uint16_t*>(find("scan.d.accid")->data), R.SD, R.CD, R.CDs, R.d_start,
-                 td.data(), dacc.data());
-        relayout(reinterpret_cast<const uint16_t*>(find("scan.k.trans")->data),
-                 reinterpret_cast<const uint16_t*>(find("scan.k.accid")->data), R.SK, R.CK, R.CKs, R.k_start,
-                 tk.data(), kacc.data());
-    }
-    R.d_start = R.k_start = 0;                                     // row offsets: the start rows are first
-    std::vector<uint32_t> cmap4(256);
-    {
-        const uint16_t* c2 = reinterpret_cast<const uint16_t*>(find("scan.cmap2")->data);
-        for (int b = 0; b < 256; ++b)
-            cmap4[b] = (SCAN_TD_BASE + 2u * (c2[b] & 0xffu)) | (tk_base + 2u * (uint32_t)(c2[b] >> 8)) << 16;
-    }
-    std::vector<uint16_t> k_acc_min;
-    {
-        const Section* so = find("scan.k.acc_off");
-        const uint32_t* off = reinterpret_cast<const uint32_t*>(so->data);
-        const uint16_t* ids = reinterpret_cast<const uint16_t*>(find("scan.k.acc_ids")->data);
-        const size_t nsets = so->bytes / 4 - 1;
-        R.n_kacc = (uint32_t)nsets;
-        R.n_dacc = (uint32_t)(find("scan.d.acc_off")->bytes / 4 - 1);
-        for (size_t a = 0; a < nsets; ++a) {
-            int m = KW_NONE;
-            for (uint32_t i = off[a]; i < off[a + 1]; ++i) m = std::min<int>(m, ids[i]);
-            k_acc_min.push_back((uint16_t)m);
-        }
-    }
-    R.kw_always_min = KW_NONE;
-    {
-        const uint8_t* al = find("kw.always")->data;
-        for (int g = 0; g < R.G; ++g)
-            if (al[g]) {
-                R.kw_always_min = g;
-                break;
-            }
-    }
-    {
-        const uint8_t* ex = find("det.exidx")->data;
-        int ne = 0;
-        for (int p = 0; p < R.P; ++p)
-            if (ex[p] != 0xff) ne = std::max(ne, ex[p] + 1);
-        if (ne > NE_MAX) return fail("too many excluder patterns");
-        R.NE = ne;
-    }
-    // deidentify_config: without the sections every type is replaced by its "[NAME]" token
-    e->xf_kind.assign(R.T, (uint8_t)PII_XF_INFO_TYPE);
-    std::vector<uint32_t> xf_maskp((size_t)std::max(R.T, 1) * XF_MASK_WORDS, 0u);
-    const Section* xs_repl_off = nullptr;
-    const Section* xs_repl = nullptr;
-    const Section* xs_hkey = nullptr;
-    const Section* xs_hmid = nullptr;
-    if (const Section* xk = find("xf.kind")) {
-        xs_repl_off = find("xf.repl_off");
-        xs_repl = find("xf.repl");
-        const Section* xm = find("xf.mask");
-        if (xk->bytes != (size_t)R.T || !xs_repl_off || !xs_repl || !xm || xs_repl_off->bytes != ((size_t)R.T + 1) * 4 ||
-            xm->bytes != (size_t)R.T * XF_MASK_WORDS * 4)
-            return fail("transformation tables malformed");
-        const uint32_t* ro = reinterpret_cast<const uint32_t*>(xs_repl_off->data);
-        for (int t = 0; t < R.T; ++t) {
-            if (xk->data[t] > PII_XF_HASH || ro[t] > ro[t + 1] || ro[t + 1] > xs_repl->bytes || ro[t + 1] - ro[t] > 255)
-                return fail("transformation tables malformed");
-            e->xf_kind[t] = xk->data[t];
-            e->xf_src |= xk->data[t] == PII_XF_MASK || xk->data[t] == PII_XF_KEEP;
-            e->xf_mask |= xk->data[t] == PII_XF_MASK;
-            e->xf_hash |= xk->data[t] == PII_XF_HASH;
-        }
-        if (e->xf_hash) {   // per type a key index, per key two midstates; a hash type's replacement is its placeholder
-            xs_hkey = find("xf.hash_key");
-            xs_hmid = find("xf.hash_mid");
-            if (!xs_hkey || !xs_hmid || xs_hkey->bytes != (size_t)R.T * 4 || xs_hmid->bytes == 0 ||
-                xs_hmid->bytes % (XF_HASH_KEY_WORDS * 4) != 0)
-                return fail("transformation tables malformed");
-            const uint32_t* hk = reinterpret_cast<const uint32_t*>(xs_hkey->data);
-            for (int t = 0; t < R.T; ++t)
-                if (e->xf_kind[t] == PII_XF_HASH &&
-                    (hk[t] >= xs_hmid->bytes / (XF_HASH_KEY_WORDS * 4) || ro[t + 1] - ro[t] != XF_HASH_LEN))
-                    return fail("transformation tables malformed");
-        }
-        std::memcpy(xf_maskp.data(), xm->data, xm->bytes);
-        for (int t = 0; t < R.T; ++t)
-            if (e->xf_kind[t] == PII_XF_MASK && (xf_maskp[(size_t)t * XF_MASK_WORDS] & 0xffu) > 127u)
-                return fail("transformation tables malformed");
-    }
-    // tok_len: the per-type output length table behind out_len (T + 1 entries, as the offsets it replaces
-    // in the k_select / k_win_select images)
-    std::vector<uint32_t> tok_off(R.T + 1, 0), tok_len(R.T + 1, 0);
-    std::string tok;
-    for (int t = 0; t < R.T; ++t) {
-        if (e->xf_kind[t] == PII_XF_INFO_TYPE) {
-            tok += "[" + e->names[t] + "]";
-        } else if (e->xf_kind[t] == PII_XF_REPLACE || e->xf_kind[t] == PII_XF_HASH) {   // (hash: the placeholder)
-            const uint32_t* ro = reinterpret_cast<const uint32_t*>(xs_repl_off->data);
-            tok.append(reinterpret_cast<const char*>(xs_repl->data) + ro[t], ro[t + 1] - ro[t]);
-        }
-        tok_off[t + 1] = (uint32_t)tok.size();
-        const bool same_len = e->xf_kind[t] == PII_XF_MASK || e->xf_kind[t] == PII_XF_KEEP;
-        tok_len[t] = same_len ? XF_SAME_LEN : tok_off[t + 1] - tok_off[t];
-    }
-    tok += "\n";               // the re-scan window separator (k_win_redact piece source)
-    R.nl_off = (uint32_t)tok.size() - 1;
-    tok.append(32, '\0');     // k_redact reads aligned 16-byte windows past a token's end
-    // SCAN groups >= 1: their own D automaton and class map, a 1-row never-accepting K stub
-    struct HostGroup {
-        int SD, CD, CDs, start, dsh;
-        uint32_t lds;
-        std::vector<uint16_t> td, tk, dacc, kacc, npair;
-        std::vector<uint32_t> cmap4;
-    };
-    std::vector<HostGroup> hg;
-    {
-        const int64_t n_extra = meta[14];
-        if (n_extra < 0 || n_extra + 1 > SCAN_GROUPS_MAX) return fail("too many SCAN groups");
-        const Section* gs = find("scan.groups");
-        if (n_extra > 0 && (!gs || gs->bytes < (size_t)n_extra * 32)) return fail("SCAN group table missing");
-        for (int64_t q = 1; q <= n_extra; ++q) {
-            const int64_t* gm = reinterpret_cast<const int64_t*>(gs->data) + 4 * (q - 1);
-            const std::string nm = "scan.g" + std::to_string(q);
-            const Section *sc = find((nm + ".cmap").c_str()), *st = find((nm + ".trans").c_str()),
-                          *sa = find((nm + ".accid").c_str());
-            HostGroup h;
-            h.SD = (int)gm[0];
-            h.CD = (int)gm[1];
-            h.CDs = (h.CD + 1) & ~1;
-            h.dsh = 0;
-            if (!sc || !st || !sa || st->bytes != (size_t)h.SD * h.CD * 2 || sa->bytes != st->bytes || sc->bytes != 256)
-                return fail("SCAN group tables malformed");
-            // a table past 64 KiB of LDS addresses is WIDE: rows padded to a multiple of 4 entries (8-byte
-            // aligned), entries hold the row offset / 2, so 16-bit entries reach 128 KiB (and the u16
-            // transition index of an event, 64k entries)
-            if (SCAN_TD_BASE + (size_t)h.SD * h.CDs * 2 + 4 + SCAN_SPREAD_BYTES > 65536) {
-                h.CDs = (h.CD + 3) & ~3;
-                h.dsh = 1;
-                if ((size_t)h.SD * h.CDs > 65536) return fail("a SCAN group exceeds 128 KiB of LDS");
-            }
-            const uint32_t tkb = SCAN_TD_BASE + (uint32_t)(h.SD * h.CDs) * 2;
-            h.lds = tkb + 4 + SCAN_SPREAD_BYTES;                // + the K stub's row (2 entries), spread masks
-            if (h.lds + FIX_LDS > 160 * 1024) return fail("a SCAN group exceeds the LDS");
-            h.td.assign((size_t)h.SD * h.CDs, 0);
-            h.dacc.assign((size_t)h.SD * h.CDs, 0);
-            if (gm[2] < 0 || gm[2] >= h.SD) return fail("SCAN group start state out of range");
-            relayout(reinterpret_cast<const uint16_t*>(st->data), reinterpret_cast<const uint16_t*>(sa->data), h.SD,
-                     h.CD, h.CDs, (int)gm[2], h.td.data(), h.dacc.data(), h.dsh);
-            h.tk = {0, 0};
-            h.kacc = {0, 0};
-            h.start = 0;
-            h.cmap4.resize(256);
-            // class words of a group >= 1: the D half only (its K is the stub, stepped at tk_base)
-            for (int b = 0; b < 256; ++b) h.cmap4[b] = SCAN_TD_BASE + 2u * sc->data[b];
-            hg.push_back(std::move(h));
-        }
-    }
-    // one device buffer holding every table, 256-byte aligned sections
-    struct Put {
-        const void* src;
-        size_t bytes;
-        size_t off;
-    };
-    std::vector<Put> puts;
-    size_t total = 0;
-    auto add = [&](const void* src, size_t bytes) {
-        total = (total + 255) & ~(size_t)255;
-        puts.push_back({src, bytes, total});
-        total += bytes + 16;
-        return puts.size() - 1;
-    };
-    auto addsec = [&](const char* nm) { return add(find(nm)->data, find(nm)->bytes); };
-    size_t i_cmap = add(cmap4.data(), cmap4.size() * 4), i_td = add(td.data(), td.size() * 2), i_tk = add(tk.data(), tk.size() * 2);
-    size_t i_dacc = add(dacc.data(), dacc.size() * 2), i_doff = addsec("scan.d.acc_off"), i_dids = addsec("scan.d.acc_ids");
-    size_t i_kacc = add(kacc.data(), kacc.size() * 2), i_kmin = add(k_acc_min.data(), k_acc_min.size() * 2);
-    std::vector<uint16_t> d_npair(dacc.size()), k_grp(kacc.size());
-    {
-        const uint32_t* off = reinterpret_cast<const uint32_t*>(find("scan.d.acc_off")->data);
-        for (size_t i = 0; i < dacc.size(); ++i) d_npair[i] = (uint16_t)(off[dacc[i] + 1] - off[dacc[i]]);
-        for (size_t i = 0; i < kacc.size(); ++i) k_grp[i] = kacc[i] ? k_acc_min[kacc[i]] : (uint16_t)KW_NONE;
-        for (auto& h : hg) {
-            h.npair.resize(h.dacc.size());
-            for (size_t i = 0; i < h.dacc.size(); ++i) h.npair[i] = (uint16_t)(off[h.dacc[i] + 1] - off[h.dacc[i]]);
-        }
-    }
-    std::vector<uint32_t> d_na(dacc.size());
-    for (size_t i = 0; i < dacc.size(); ++i) d_na[i] = d_npair[i] | (uint32_t)dacc[i] << 16;
-    size_t i_dnp = add(d_npair.data(), d_npair.size() * 2), i_kgrp = add(k_grp.data(), k_grp.size() * 2);
-    size_t i_dna = add(d_na.data(), d_na.size() * 4);
-    size_t i_dt = addsec("det.type"), i_dv = addsec("det.validator"), i_dl = addsec("det.lik"),
-           i_dx = addsec("det.exidx"), i_fd = addsec("det.first_desc"), i_hr = addsec("hot.rule"),
-           i_hd = addsec("hot.dfa_desc"), i_ve = addsec("var.enabled"), i_vm = addsec("var.minlik"),
-           i_ro = addsec("var.rule_off"), i_ri = addsec("var.rule_ids"), i_eo = addsec("var.excl_off"),
-           i_ei = addsec("var.excl_ids"), i_to = add(tok_off.data(), tok_off.size() * 4),
-           i_tb = add(tok.data(), tok.size()), i_tl = add(tok_len.data(), tok_len.size() * 4),
-           i_xk = add(e->xf_kind.data(), e->xf_kind.size()), i_xm = add(xf_maskp.data(), xf_maskp.size() * 4);
-    struct GroupPut { size_t cmap, td, tk, dacc, kacc, npair; };
-    std::vector<GroupPut> gp;
-    for (auto& h : hg)
-        gp.push_back({add(h.cmap4.data(), 1024), add(h.td.data(), h.td.size() * 2), add(h.tk.data(), 4),
-                      add(h.dacc.data(), h.dacc.size() * 2), add(h.kacc.data(), 4),
-                      add(h.npair.data(), h.npair.size() * 2)});
-    size_t i_hk = 0, i_hm = 0;      // (after every other table: rules without a hash type keep their layout)
-    if (e->xf_hash) {
-        i_hk = add(xs_hkey->data, xs_hkey->bytes);
-        i_hm = add(xs_hmid->data, xs_hmid->bytes);
-    }
-    if (hipSetDevice(device) != hipSuccess) { e->err = "hipSetDevice failed"; pii_engine_destroy(e); return PII_E_DEVICE; }
-    if (hipMalloc(&e->d_rules, total) != hipSuccess) return fail("hipMalloc rules failed");
-    std::vector<uint8_t> host(total, 0);
-    for (auto& p : puts) std::memcpy(host.data() + p.off, p.src, p.bytes);
-    if (hipMemcpy(e->d_rules, host.data(), total, hipMemcpyHostToDevice) != hipSuccess) return fail("upload failed");
-    uint8_t* b = static_cast<uint8_t*>(e->d_rules);
-    auto at = [&](size_t i) { return b + puts[i].off; };
-    R.cmap4 = (const uint32_t*)at(i_cmap);
-    R.td = (const uint16_t*)at(i_td);
-    R.tk = (const uint16_t*)at(i_tk);
-    R.d_accid = (const uint16_t*)at(i_dacc);
-    R.d_acc_off = (const uint32_t*)at(i_doff);
-    R.d_acc_ids = (const uint16_t*)at(i_dids);
-    R.k_accid = (const uint16_t*)at(i_kacc);
-    R.k_acc_min = (const uint16_t*)at(i_kmin);
-    R.d_npair = (const uint16_t*)at(i_dnp);
-    R.d_na = (const uint32_t*)at(i_dna);
-    R.k_grp = (const uint16_t*)at(i_kgrp);
-    R.det_type = (const uint16_t*)at(i_dt);
-    R.det_val = (const uint8_t*)at(i_dv);
-    R.det_lik = (const uint8_t*)at(i_dl);
-    R.det_exidx = (const uint8_t*)at(i_dx);
-    R.first_desc = (const int32_t*)at(i_fd);
-    R.hot_rule = (const int32_t*)at(i_hr);
-    R.hot_desc = (const int32_t*)at(i_hd);
-    R.var_enabled = (const uint8_t*)at(i_ve);
-    R.var_minlik = (const uint8_t*)at(i_vm);
-    R.rule_off = (const uint32_t*)at(i_ro);
-    R.rule_ids = (const uint16_t*)at(i_ri);
-    R.excl_off = (const uint32_t*)at(i_eo);
-    R.excl_ids = (const uint16_t*)at(i_ei);
-    R.tok_off = (const uint32_t*)at(i_to);
-    R.tok_bytes = (const uint8_t*)at(i_tb);
-    R.tok_len = (const uint32_t*)at(i_tl);
-    R.xf_kind = (const uint8_t*)at(i_xk);
-    R.xf_mask = (const uint32_t*)at(i_xm);
-    if (e->xf_hash) {
-        e->d_hash_key = (const uint32_t*)at(i_hk);
-        e->d_hash_mid = (const uint32_t*)at(i_hm);
-    }
-    if (R.n_dacc >= 65535) return fail("too many SCAN accept sets");
-    {   // per-kernel LDS images
-        auto sec = [&](const char* nm) { return std::make_pair((const void*)find(nm)->data, (size_t)find(nm)->bytes); };
-        const uint16_t* ptrans = (const uint16_t*)find("pool.trans")->data;
-        const uint8_t* pflags = (const uint8_t*)find("pool.flags")->data;
-        const uint8_t* pcmap = (const uint8_t*)find("pool.cmap")->data;
-        DfaPool fp, hp;
-        const int32_t* fdesc = (const int32_t*)find("det.first_desc")->data;
-        // absorbed match starts: the patterns' PRE states (absent in older blobs: nothing is dropped);
-        // PII_FIRST_DROP=0 turns the drop off
-        const Section* s_pre = find("det.first_pre");
-        if (s_pre && s_pre->bytes < (size_t)R.P * 4) return fail("det.first_pre is too short");
-        if (const char* v = std::getenv("PII_FIRST_DROP"); v && std::atoi(v) == 0) s_pre = nullptr;
-        auto fpre = [&](int p) { return s_pre ? reinterpret_cast<const int32_t*>(s_pre->data)[p] : -1; };
-        for (int p = 0; p < R.P; ++p)
-            if (fpre(p) >= fdesc[8 * p + 7]) return fail("det.first_pre names a state past its automaton");
-        bool fits = true;
-        for (int p = 0; p < R.P; ++p) fits &= add_dfa(fp, fdesc + 8 * p, ptrans, pflags, pcmap, fpre(p));
-        const int32_t* hdesc = (const int32_t*)find("hot.dfa_desc")->data;
-        for (int h = 0; h < R.n_hot; ++h) fits &= add_dfa(hp, hdesc + 8 * h, ptrans, pflags, pcmap);
-        if (!fits) return fail("a FIRST/HOT automaton has more than 16384 states");
-        if (hp.desc.empty()) hp.desc.assign(8, 0);
-        auto vec = [](const auto& v) { return std::make_pair((const void*)v.data(), v.size() * sizeof(v[0])); };
-        std::vector<std::pair<const void*, size_t>> pf(FI_N), pe(EV_N), ps(SE_N);
-        pf[FI_TRANS] = vec(fp.trans);
-        pf[FI_CMAP] = vec(fp.cmap);
-        pf[FI_DESC] = vec(fp.desc);
-        pe[EV_TRANS] = vec(hp.trans);
-        pe[EV_CMAP] = vec(hp.cmap);
-        pe[EV_HDESC] = vec(hp.desc);
-        pe[EV_HRULE] = sec("hot.rule");
-        pe[EV_DTYPE] = sec("det.type");
-        pe[EV_DVAL] = sec("det.validator");
-        pe[EV_DLIK] = sec("det.lik");
-        const size_t n_keys = (size_t)R.V * R.T;
-        const ListTab rl = dedup_lists((const uint32_t*)find("var.rule_off")->data,
-                                       (const uint16_t*)find("var.rule_ids")->data, n_keys);
-        const ListTab xl = dedup_lists((const uint32_t*)find("var.excl_off")->data,
-                                       (const uint16_t*)find("var.excl_ids")->data, n_keys);
-        const uint32_t aux = rl.w | xl.w << 3;
-        e->lists_cl = rl.w != 0 || xl.w != 0;
-        pe[EV_ROFF] = vec(rl.ix);
-        pe[EV_RLOFF] = vec(rl.loff);
-        pe[EV_RIDS] = vec(rl.ids);
-        // per type: every hotword rule it has in any context variant (k_win_eval's resident bits)
-        std::vector<uint32_t> thot(std::max(R.T, 1), 0u);
-        {
-            const uint32_t* ro = (const uint32_t*)find("var.rule_off")->data;
-            const uint16_t* ri = (const uint16_t*)find("var.rule_ids")->data;
-            for (int v = 0; v < R.V; ++v)
-                for (int t = 0; t < R.T; ++t)
-                    for (uint32_t q = ro[v * R.T + t]; q < ro[v * R.T + t + 1]; ++q)
-                        if (ri[q] < 32) thot[t] |= 1u << ri[q];     // k_win_* cache the first WHOT_BITS
-        }
-        pe[EV_THOT] = vec(thot);
-        std::vector<std::pair<const void*, size_t>> pw(WS_N);
-        pw[WS_TRANS] = vec(hp.trans);
-        pw[WS_CMAP] = vec(hp.cmap);
-        pw[WS_HDESC] = vec(hp.desc);
-        pw[WS_HRULE] = sec("hot.rule");
-        pw[WS_DTYPE] = sec("det.type");
-        pw[WS_DLIK] = sec("det.lik");
-        pw[WS_VEN] = sec("var.enabled");
-        pw[WS_VMIN] = sec("var.minlik");
-        pw[WS_DEX] = sec("det.exidx");
-        pw[WS_XOFF] = vec(xl.ix);
-        pw[WS_XLOFF] = vec(xl.loff);
-        pw[WS_XIDS] = vec(xl.ids);
-        pw[WS_TOKOFF] = std::make_pair((const void*)tok_len.data(), tok_len.size() * 4);
-        pw[WS_ROFF] = vec(rl.ix);
-        pw[WS_RLOFF] = vec(rl.loff);
-        pw[WS_RIDS] = vec(rl.ids);
-        if (!make_image(pw, e->img_wsel)) return fail("rule table upload failed");
-        e->img_wsel.li.aux = aux;
-        ps[SE_DTYPE] = sec("det.type");
-        ps[SE_VEN] = sec("var.enabled");
-        ps[SE_VMIN] = sec("var.minlik");
-        ps[SE_DEX] = sec("det.exidx");
-        ps[SE_XOFF] = vec(xl.ix);
-        ps[SE_XLOFF] = vec(xl.loff);
-        ps[SE_XIDS] = vec(xl.ids);
-        ps[SE_TOKOFF] = std::make_pair((const void*)tok_len.data(), tok_len.size() * 4);
-        if (!make_image(pf, e->img_first) || !make_image(pe, e->img_eval) || !make_image(ps, e->img_sel))
-            return fail("rule table upload failed");
-        e->img_eval.li.aux = aux;
-        e->img_sel.li.aux = aux;
-        if (e->img_first.global) {
-            // FIRST automata for k_pair_first<true>'s LDS copy: patterns in id
-            // order (the built-in types first), skipping any automaton over FIRST_HOT_BIG bytes, until
-            // the copy is full.  A skipped pattern keeps a descriptor with no columns (read from L2).
-            size_t big = FIRST_HOT_BIG, budget = FIRST_HOT_LDS;
-            if (const char* v = std::getenv("PII_FIRST_HOT_BIG")) big = (size_t)std::max(0, std::atoi(v));
-            if (const char* v = std::getenv("PII_FIRST_HOT_LDS"))
-                budget = std::min<size_t>(158 * 1024, (size_t)std::max(0, std::atoi(v)));
-            uint32_t cap_p = (uint32_t)R.P;
-            if (const char* v = std::getenv("PII_FIRST_HOT")) cap_p = std::min<uint32_t>(cap_p, (uint32_t)std::max(0, std::atoi(v)));
-            DfaPool hf;
-            uint32_t ph = 0;
-            size_t trans_n = 0, cmap_n = 0;
-            for (uint32_t p = 0; p < cap_p; ++p) {
-                const int32_t* d = fdesc + 8 * p;
-                const size_t dfa = (size_t)d[7] * d[3] * 2;
-                const size_t tr = trans_n + 64 + (size_t)d[7] * d[3];
-                const size_t bytes = ((tr * 2 + 15) & ~(size_t)15) + ((cmap_n + 260 + 15) & ~(size_t)15) +
-                                     (((size_t)(p + 1) * 32 + 15) & ~(size_t)15);
-                if (bytes > budget) {
-                    if (big == 0) break;
-                    continue;
-                }
-                if (big && dfa > big) continue;
-                trans_n = tr;
-                cmap_n += 260;
-                ph = p + 1;
-            }
-            if (ph > 0) {
-                trans_n = 0;
-                for (uint32_t p = 0; p < ph; ++p) {
-                    const int32_t* d = fdesc + 8 * p;
-                    const size_t dfa = (size_t)d[7] * d[3] * 2;
-                    const size_t tr = hf.trans.size() + 64 + (size_t)d[7] * d[3];
-                    const size_t bytes = ((tr * 2 + 15) & ~(size_t)15) + ((hf.cmap.size() + 260 + 15) & ~(size_t)15) +
-                                         (((size_t)ph * 32 + 15) & ~(size_t)15);
-                    if ((big && dfa > big) || bytes > budget) {
-                        hf.desc.insert(hf.desc.end(), 8, 0);          // columns 0: not resident
-                        continue;
-                    }
-                    add_dfa(hf, d, ptrans, pflags, pcmap, fpre((int)p));
-                }
-                std::vector<std::pair<const void*, size_t>> ph_parts(FI_N);
-                ph_parts[FI_TRANS] = vec(hf.trans);
-                ph_parts[FI_CMAP] = vec(hf.cmap);
-                ph_parts[FI_DESC] = vec(hf.desc);
-                if (!make_image(ph_parts, e->img_first_hot)) return fail("rule table upload failed");
-                if (e->img_first_hot.li.total > 64 * 1024 &&
-                    hipFuncSetAttribute((const void*)k_pair_first<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)e->img_first_hot.li.total) != hipSuccess)
-                    return fail("cannot raise the LDS limit of k_pair_first");
-                e->first_p_hot = ph;
-            }
-        }
-        if (e->img_eval.li.total > IMG_LDS_SPLIT) {
-            auto pr = pe;
-            pr[EV_ROFF] = std::make_pair((const void*)nullptr, (size_t)0);
-            pr[EV_RLOFF] = std::make_pair((const void*)nullptr, (size_t)0);
-            pr[EV_RIDS] = std::make_pair((const void*)nullptr, (size_t)0);
-            if (!make_image(pr, e->img_eval_rg)) return fail("rule table upload failed");
-            if (e->img_eval_rg.global || (e->img_eval_rg.li.total > 64 * 1024 &&
-                                          hipFuncSetAttribute((const void*)k_pair_eval<false, true>,
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                              (int)e->img_eval_rg.li.total) != hipSuccess)) {
-                (void)hipFree(e->img_eval_rg.d);
-                e->img_eval_rg = DevImage{};
-            }
-        }
-        if (e->img_sel.li.total > IMG_LDS_SPLIT) {
-            auto pr = ps;
-            pr[SE_XOFF] = std::make_pair((const void*)nullptr, (size_t)0);
-            pr[SE_XLOFF] = std::make_pair((const void*)nullptr, (size_t)0);
-            pr[SE_XIDS] = std::make_pair((const void*)nullptr, (size_t)0);
-            if (!make_image(pr, e->img_sel_rg)) return fail("rule table upload failed");
-            if (e->img_sel_rg.global || e->img_sel_rg.li.total > 64 * 1024) {      // (no gain: keep the full image)
-                (void)hipFree(e->img_sel_rg.d);
-                e->img_sel_rg = DevImage{};
-            }
-        }
-        // (the window re-scan's kernels read an image past LDS in place, like the pair kernels)
-        const std::pair<const void*, const DevImage*> big[] = {
-            {(const void*)k_pair_first<false>, &e->img_first}, {(const void*)k_pair_eval<false>, &e->img_eval},
-            {(const void*)k_select<false, false>, &e->img_sel}, {(const void*)k_sel_fix<false, false>, &e->img_sel},
-            {(const void*)k_select<false, true>, &e->img_sel}, {(const void*)k_sel_fix<false, true>, &e->img_sel},
-            {(const void*)k_select<false, false, true>, &e->img_sel},
-            {(const void*)k_sel_fix<false, false, true>, &e->img_sel},
-            {(const void*)k_select<false, true, true>, &e->img_sel}, {(const void*)k_sel_fix<false, true, true>, &e->img_sel},
-            {(const void*)k_pair_eval<false, false, true>, &e->img_eval},
-            {(const void*)k_win_eval<false>, &e->img_eval},
-            {(const void*)k_win_select<false>, &e->img_wsel}};
-        // k_win_halo<false>: its image plus HALO_LDS of tables (the launch falls back to <true> past the LDS)
-        if (hipFuncSetAttribute((const void*)k_win_halo<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)IMG_LDS_MAX) != hipSuccess)
-            return fail("cannot raise the LDS limit of k_win_halo");
-        for (auto& kb : big)
-            if (!kb.second->global && kb.second->li.total > 64 * 1024 &&
-                hipFuncSetAttribute(kb.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kb.second->li.total) !=
-                    hipSuccess)
-                return fail("cannot raise the LDS limit of a pair kernel");
-        if (const char* v = std::getenv("PII_VERBOSE"); v && std::atoi(v) > 0) {
-            const std::pair<const char*, const DevImage*> ims[] = {
-                {"first", &e->img_first}, {"first_hot", &e->img_first_hot}, {"eval", &e->img_eval},
-                {"eval_rg", &e->img_eval_rg}, {"sel", &e->img_sel}, {"sel_rg", &e->img_sel_rg}, {"wsel", &e->img_wsel}};
-            for (auto& im : ims)
-                if (im.second->d)
-                    std::fprintf(stderr, "pii: image %-9s %8u bytes %s\n", im.first, im.second->li.total,
-                                 im.second->global ? "global" : "lds");
-        }
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-            e->n_cu = prop.multiProcessorCount;
-        // k_pair_first: two 1024-thread workgroups per CU, one round (2 or 4 rounds: 160 -> 165 / 164 µs,
-        // and k_pair_eval slower on the smaller segments)
-        e->n_seg = 2 * (uint32_t)e->n_cu;
-        // k_pair_eval work units per k_pair_first workgroup: 2 (config 2: 1 / 2 / 3 / 4 -> 342 / 312 / 315
-        // / 318 us); 4 for a large rule set (config 5's longer evaluations: 2 -> 4: 909 -> 893 us)
-        if ((size_t)R.V * R.T > LIST_DEDUP_KEYS) e->eval_split = 4;
-        if (const char* v = std::getenv("PII_EVAL_SPLIT")) e->eval_split = (uint32_t)std::max(1, std::min(64, std::atoi(v)));
-        if (const char* v = std::getenv("PII_MERGE_CAP")) e->merge_cap = (uint32_t)std::max(0, std::min(MERGE_EVW, std::atoi(v)));
-        if (hipMalloc(&e->mcount, e->n_seg * PAIR_WAVES * sizeof(uint32_t)) != hipSuccess) return fail("hipMalloc failed");
-    }
-    e->scan_lds = SCAN_TD_BASE + (size_t)(R.SD * R.CDs / 2) * 4 + (size_t)(R.SK * R.CKs / 2) * 4 + SCAN_SPREAD_BYTES;
-    if (e->scan_lds > 160 * 1024) return fail("SCAN tables do not fit in LDS");
-    e->n_sg = 1 + (uint32_t)hg.size();
-    e->sg.assign(1, R);
-    e->sg_lds.assign(1, e->scan_lds);
-    e->acct.accid[0] = R.d_accid;
-    e->acct.npair[0] = R.d_npair;
-    for (size_t q = 0; q < hg.size(); ++q) {
-        RulesDev Rq = R;
-        const HostGroup& h = hg[q];
-        Rq.cmap4 = (const uint32_t*)at(gp[q].cmap);
-        Rq.td = (const uint16_t*)at(gp[q].td);
-        Rq.tk = (const uint16_t*)at(gp[q].tk);
-        Rq.d_accid = (const uint16_t*)at(gp[q].dacc);
-        Rq.k_accid = (const uint16_t*)at(gp[q].kacc);
-        Rq.d_npair = (const uint16_t*)at(gp[q].npair);
-        Rq.SD = h.SD;
-        Rq.CD = h.CD;
-        Rq.CDs = h.CDs;
-        Rq.dsh = h.dsh;
-        Rq.d_start = h.start;
-        Rq.SK = 1;
-        Rq.CK = 2;
-        Rq.CKs = 2;
-        Rq.k_start = 0;
-        e->sg.push_back(Rq);
-        e->sg_lds.push_back(h.lds);
-        e->acct.accid[q + 1] = Rq.d_accid;
-        e->acct.npair[q + 1] = Rq.d_npair;
-    }
-    const size_t max_lds = *std::max_element(e->sg_lds.begin(), e->sg_lds.end());
-    e->max_sg_lds = max_lds;
-    {
-        std::vector<uint32_t> lds32(e->sg_lds.begin(), e->sg_lds.end());
-        if (hipMalloc(&e->d_sg, e->sg.size() * sizeof(RulesDev)) != hipSuccess ||
-            hipMalloc(&e->d_sg_lds, lds32.size() * 4) != hipSuccess ||
-            hipMemcpy(e->d_sg, e->sg.data(), e->sg.size() * sizeof(RulesDev), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(e->d_sg_lds, lds32.data(), lds32.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return fail("hipMalloc failed");
-    }
-    if (const char* v = std::getenv("PII_SCAN_COUNT")) e->scan_count = std::atoi(v) != 0;
-    if (const char* v = std::getenv("PII_LONG_GATE")) e->long_gate = std::atoi(v) != 0;
-    if (const char* v = std::getenv("PII_SCAN_ILV")) e->scan_ilv = std::atoi(v) != 0;
-    if (const char* v = std::getenv("PII_WIN_LONG")) e->win_long = (uint32_t)std::max(0, std::min(64, std::atoi(v)));
-    if (const char* v = std::getenv("PII_HALO_ITEMS")) e->halo_items = (uint32_t)std::max(0, std::min(HALO_ITEMS, std::atoi(v)));
-    if (const char* v = std::getenv("PII_TIMING")) e->timing = std::max(0, std::min(2, std::atoi(v)));
-    if (max_lds > 64 * 1024 &&
-        (hipFuncSetAttribute((const void*)k_scan<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds) !=
-             hipSuccess ||
-         hipFuncSetAttribute((const void*)k_scan<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds) !=
-             hipSuccess ||
-         hipFuncSetAttribute((const void*)k_scan<false, SCAN_BLOCK_WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)max_lds) != hipSuccess))
-        return fail("cannot raise LDS limit");
-    if (max_lds + FIX_LDS > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)k_scan_fix, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(max_lds + FIX_LDS)) != hipSuccess)
-        return fail("cannot raise LDS limit");
-    e->hist_types = (uint32_t)std::min(R.T, 1024);
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) return fail("stream");
-    e->own_stream = true;
-    if (e->n_sg > 1) {
-        int ns_scan = SCAN_STREAMS;
-        if (const char* v = std::getenv("PII_SCAN_STREAMS")) ns_scan = std::max(1, std::min(3, std::atoi(v)));
-        e->n_aux = (uint32_t)ns_scan - 1;
-        if (e->n_aux && hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess) return fail("event");
-        for (uint32_t i = 0; i < e->n_aux; ++i)
-            if (hipStreamCreateWithFlags(&e->aux[i], hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&e->ev_join[i], hipEventDisableTiming) != hipSuccess)
-                return fail("stream");
-    }
-    for (auto& t : e->kev)
-        if (hipEventCreate(&t) != hipSuccess) return fail("event");
-    for (auto& t : e->tev)
-        if (hipEventCreate(&t) != hipSuccess) return fail("event");
-    const size_t ns = std::max<uint32_t>(1, n_conv_slots);
-    if (hipMalloc(&e->st_group, ns * 4) != hipSuccess || hipMalloc(&e->st_ts, ns * 8) != hipSuccess ||
-        hipMalloc(&e->stamp, ns * 4) != hipSuccess ||
-        hipMalloc(&e->d_err, 64) != hipSuccess || hipMalloc(&e->d_totals, hist_bytes(e)) != hipSuccess ||
-        hipMalloc(&e->lb_ticket, 32) != hipSuccess ||
-        hipMemset(e->lb_ticket, 0, 32) != hipSuccess)
-        return fail("state allocation failed");
-    e->long_count = e->d_err + 1;
-    e->ncommit = e->d_err + 2;
-    e->pair_count = reinterpret_cast<unsigned long long*>(e->d_err + 4);
-    // the histogram lives right after the totals, so one async copy at the end of a call brings both
-    e->hist = reinterpret_cast<unsigned long long*>(e->d_totals + 8);
-    if (hipHostMalloc(&e->h_totals, hist_bytes(e)) != hipSuccess) return fail("pinned allocation failed");
-    std::vector<int32_t> g(ns, -1);
-    if (hipMemcpy(e->st_group, g.data(), ns * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(e->st_ts, 0, ns * 8) != hipSuccess || hipMemset(e->stamp, 0, ns * 4) != hipSuccess ||
-        hipMemset(e->hist, 0, std::max(R.T, 256) * 8) != hipSuccess)
-        return fail("state init failed");
-    k_noop<<<1, 64, 0, e->stream>>>();
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return fail("device not usable");
     *out = e;
     return PII_OK;
 }
 
+// Work buffers (grow) are freed from their accounting; the list below holds what is allocated elsewhere.
 int pii_engine_destroy(pii_engine* e) {
     if (!e) return PII_E_ARG;
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    void* ptrs[] = {e->d_rules, e->st_group, e->st_ts, e->stamp, e->ev, e->fd, e->n_ev, e->n_find,
-                    e->out_len, e->incl, e->agg_f, e->first_utt, e->lane_perm, e->lane_pos, e->lane_bkt, e->lane_cnt, e->bnd, e->hist_part, e->evloc, e->lane_ev, e->pres, e->pend, e->lane_pair, e->lane_np, e->matched, e->mcount, e->cont,
-                    e->img_first.d, e->img_first_hot.d, e->img_eval.d, e->img_eval_rg.d, e->img_sel.d, e->img_sel_rg.d, e->kw, e->ctx, e->agg_v, e->commit,
-                    e->span_offs, e->bsum, e->out_offs_tmp, e->lb_state, e->lb_ticket, e->d_err, e->d_totals, e->h_text, e->h_role,
-                    e->h_out, e->h_offs, e->h_out_offs, e->h_slot, e->h_ts, e->h_spans, e->h_ctx,
-                    e->img_wsel.d, e->wr_desc, e->wr_cnt, e->wr_head, e->wr_arena, e->wc, e->phot, e->wc_first,
-                    e->wc_n, e->wbound, e->n_wfind, e->wout_len, e->wfbase, e->wspan_offs, e->wnew, e->wctx, e->wfd,
-                    e->long_rows, e->lane_st, e->lane_geo, e->lane_evn, e->lane_nf, e->lane_rd, e->lane_reach, e->lane_rowbase,
-                    e->dirty, e->lane_sp, e->spill, e->rsp, e->tile_first, e->h_ext, e->h_ext_n, e->jbuf, e->joff,
-                    e->jlen, e->kw2, e->jrole, e->err_saved, e->d_sg, e->d_sg_lds};
+    for (auto& kv : e->scratch_sizes) (void)hipFree(kv.first);
+    void* ptrs[] = {e->d_rules, e->img_first.d, e->img_first_hot.d, e->img_eval.d, e->img_eval_rg.d, e->img_sel.d,
+                    e->img_sel_rg.d, e->img_wsel.d, e->mcount, e->d_sg, e->d_sg_lds, e->st_group, e->st_ts, e->stamp,
+                    e->d_err, e->d_totals, e->lb_ticket};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    free_window_tables(e->wr);
     if (e->h_totals) (void)hipHostFree(e->h_totals);
     if (e->h_jtotal) (void)hipHostFree(e->h_jtotal);
     for (auto& t : e->tev)
@@ -6681,8 +6106,9 @@ int pii_scan_redact_device(pii_engine* e, const uint8_t* d_bytes, const uint64_t
                            const uint32_t* d_slot, const uint8_t* d_role, const int64_t* d_ts, uint8_t* d_out,
                            uint64_t out_cap, uint64_t* d_out_offsets, pii_span* d_spans, uint32_t span_cap,
                            int16_t* d_ctx_info, void* stream) {
-    return device_call(e, false, d_bytes, d_offsets, n_utt, d_slot, d_role, d_ts, d_out, out_cap, d_out_offsets,
-                       d_spans, span_cap, d_ctx_info, stream, nullptr);
+    Call c = call_rows(d_bytes, d_offsets, n_utt, d_slot, d_role, d_ts);
+    return device_call(e, false, with_out(c, d_out, out_cap, d_out_offsets, d_spans, span_cap, d_ctx_info), stream,
+                       nullptr);
 }
 
 int pii_scan_redact_device_ex(pii_engine* e, const uint8_t* d_bytes, const uint64_t* d_offsets, uint32_t n_utt,
@@ -6690,8 +6116,8 @@ int pii_scan_redact_device_ex(pii_engine* e, const uint8_t* d_bytes, const uint6
                               const int64_t* d_ts, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offsets,
                               pii_span* d_spans, uint32_t span_cap, int16_t* d_ctx_info, void* stream) {
     const uint64_t decl[2] = {batch_base, batch_bytes};
-    return device_call(e, false, d_bytes, d_offsets, n_utt, d_slot, d_role, d_ts, d_out, out_cap, d_out_offsets,
-                       d_spans, span_cap, d_ctx_info, stream, decl);
+    Call c = call_rows(d_bytes, d_offsets, n_utt, d_slot, d_role, d_ts);
+    return device_call(e, false, with_out(c, d_out, out_cap, d_out_offsets, d_spans, span_cap, d_ctx_info), stream, decl);
 }
 
 int pii_reserve(pii_engine* e, uint32_t max_utt, uint64_t max_bytes, uint64_t max_out, uint32_t max_spans) {
@@ -6762,15 +6188,15 @@ int pii_sync(pii_engine* e, uint64_t totals[3]) {
     float tot = 0;
     for (int i = 0; i < 5; ++i) {
         float ms = 0;
-        if (e->timing >= 2) HIPCHK(hipEventElapsedTime(&ms, e->tev[i], e->tev[i + 1]));
+        if (e->k.timing >= 2) HIPCHK(hipEventElapsedTime(&ms, e->tev[i], e->tev[i + 1]));
         e->last_ms[i] = ms;
         tot += ms;
     }
     // (level 1: the call from its start to its completion event, the totals' copy included)
-    if (e->timing == 1) HIPCHK(hipEventElapsedTime(&tot, e->tev[0], e->tev[6]));
+    if (e->k.timing == 1) HIPCHK(hipEventElapsedTime(&tot, e->tev[0], e->tev[6]));
     e->last_ms[5] = tot;
     e->last_kms[0] = e->last_kms[1] = 0.f;
-    if (e->kev_valid && e->timing >= 1) {
+    if (e->kev_valid && e->k.timing >= 1) {
         HIPCHK(hipEventElapsedTime(&e->last_kms[0], e->kev[0], e->kev[1]));
         HIPCHK(hipEventElapsedTime(&e->last_kms[1], e->kev[2], e->kev[3]));
     }
@@ -6807,7 +6233,7 @@ int pii_sync(pii_engine* e, uint64_t totals[3]) {
 int pii_set_timing(pii_engine* e, int level) {
     if (!e || level < 0 || level > 2) return PII_E_ARG;
     HIPCHK(hipStreamSynchronize(e->stream));      // (no call in flight records under the old level)
-    e->timing = level;
+    e->k.timing = level;
     return PII_OK;
 }
 
@@ -6846,17 +6272,16 @@ int pii_last_timings_ex(pii_engine* e, float* ms, uint32_t n) {
 }  // extern "C"
 
 namespace {
-// host-buffer calls: stage the rows through the engine's device buffers, run, wait, copy back
-int host_call(pii_engine* e, bool window, const uint8_t* bytes, const uint64_t* offsets, uint32_t n_utt,
-              const uint32_t* conv_slot, const uint8_t* role, const int64_t* ts_us, uint8_t* out_bytes,
-              uint64_t out_cap, uint64_t* out_offsets, pii_span* spans, uint32_t span_cap, uint32_t* n_spans,
-              int16_t* ctx_info, const ExtArgs* x = nullptr) {
-    if (!e || !offsets || !out_offsets || (n_utt && (!conv_slot || !role))) return PII_E_ARG;
-    if (x && (!x->ext || !x->ext_n || x->stride == 0)) return PII_E_ARG;
+// host-buffer calls: stage the rows through the engine's device buffers, run, wait, copy back.
+// stage_rows: checks the offsets, uploads the rows of `h` (host pointers) and fills `d`, the call over
+// the staged copies (batch base 0, the engine's stream, ctx_info in the engine's buffer).
+int stage_rows(pii_engine* e, const Call& h, Call& d) {
+    if (!h.offs || (h.n_utt && (!h.slot || !h.role))) return PII_E_ARG;
+    const uint32_t n_utt = h.n_utt;
     for (uint32_t i = 0; i < n_utt; ++i)
-        if (offsets[i + 1] < offsets[i]) return PII_E_ARG;
+        if (h.offs[i + 1] < h.offs[i]) return PII_E_ARG;
     HIPCHK(hipSetDevice(e->device));
-    const uint64_t base = offsets[0], total = offsets[n_utt] - base;
+    const uint64_t base = h.offs[0], total = h.offs[n_utt] - base;
     int rc;
     if (total + 16 > e->cap_h_bytes) {
         const uint64_t nb = total + total / 8 + 64;
@@ -6871,28 +6296,42 @@ int host_call(pii_engine* e, bool window, const uint8_t* bytes, const uint64_t* 
             return rc;
         e->cap_h_utt = nu;
     }
-    if (out_cap + 16 > e->cap_h_out) {
-        const uint64_t nb = out_cap + 64;
+    hipStream_t st = e->stream;
+    e->rel.resize(n_utt + 1);           // (lives until the call's pii_sync: the copy below is asynchronous)
+    for (uint32_t i = 0; i <= n_utt; ++i) e->rel[i] = h.offs[i] - base;
+    if (total) HIPCHK(hipMemcpyAsync(e->h_text, h.text + base, total, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->h_offs, e->rel.data(), (n_utt + 1) * 8, hipMemcpyHostToDevice, st));
+    if (n_utt) {
+        HIPCHK(hipMemcpyAsync(e->h_slot, h.slot, n_utt * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(e->h_role, h.role, n_utt, hipMemcpyHostToDevice, st));
+        if (h.ts) HIPCHK(hipMemcpyAsync(e->h_ts, h.ts, n_utt * 8, hipMemcpyHostToDevice, st));
+    }
+    d = call_rows(e->h_text, e->h_offs, n_utt, e->h_slot, e->h_role, h.ts ? e->h_ts : nullptr);
+    d.total = total;
+    d.ctx_info = e->h_ctx;
+    d.st = st;
+    return PII_OK;
+}
+
+int host_call(pii_engine* e, bool window, const Call& h, uint32_t* n_spans) {
+    if (!e || !h.out_offs) return PII_E_ARG;
+    Call d;
+    int rc = stage_rows(e, h, d);
+    if (rc) return rc;
+    const uint32_t n_utt = h.n_utt;
+    if (h.out_cap + 16 > e->cap_h_out) {
+        const uint64_t nb = h.out_cap + 64;
         if ((rc = grow(e, e->h_out, nb))) return rc;
         e->cap_h_out = nb;
     }
-    if (span_cap + 1 > e->cap_h_spans) {
-        const uint32_t ns = span_cap + 64;
+    if (h.span_cap + 1 > e->cap_h_spans) {
+        const uint32_t ns = h.span_cap + 64;
         if ((rc = grow(e, e->h_spans, ns))) return rc;
         e->cap_h_spans = ns;
     }
-    hipStream_t st = e->stream;
-    std::vector<uint64_t> rel(n_utt + 1);
-    for (uint32_t i = 0; i <= n_utt; ++i) rel[i] = offsets[i] - base;
-    if (total) HIPCHK(hipMemcpyAsync(e->h_text, bytes + base, total, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(e->h_offs, rel.data(), (n_utt + 1) * 8, hipMemcpyHostToDevice, st));
-    if (n_utt) {
-        HIPCHK(hipMemcpyAsync(e->h_slot, conv_slot, n_utt * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(e->h_role, role, n_utt, hipMemcpyHostToDevice, st));
-        if (ts_us) HIPCHK(hipMemcpyAsync(e->h_ts, ts_us, n_utt * 8, hipMemcpyHostToDevice, st));
-    }
-    if (x && n_utt) {          // stage the external spans (stride-padded rows) next to the text
-        const uint64_t ne = (uint64_t)n_utt * x->stride;
+    with_out(d, e->h_out, h.out_cap, e->h_out_offs, e->h_spans, h.span_cap, e->h_ctx);
+    if (h.ext && n_utt) {          // stage the external spans (stride-padded rows) next to the text
+        const uint64_t ne = (uint64_t)n_utt * h.ext_stride;
         if (ne > e->cap_h_ext) {
             if ((rc = grow(e, e->h_ext, ne))) return rc;
             e->cap_h_ext = ne;
@@ -6901,97 +6340,56 @@ int host_call(pii_engine* e, bool window, const uint8_t* bytes, const uint64_t* 
             if ((rc = grow(e, e->h_ext_n, (size_t)n_utt + n_utt / 8 + 64))) return rc;
             e->cap_h_ext_n = n_utt + n_utt / 8 + 64;
         }
-        HIPCHK(hipMemcpyAsync(e->h_ext, x->ext, ne * sizeof(pii_span), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(e->h_ext_n, x->ext_n, (size_t)n_utt * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(e->h_ext, h.ext, ne * sizeof(pii_span), hipMemcpyHostToDevice, d.st));
+        HIPCHK(hipMemcpyAsync(e->h_ext_n, h.ext_n, (size_t)n_utt * 4, hipMemcpyHostToDevice, d.st));
     }
-    if (window)
-        rc = run_window(e, e->h_text, e->h_offs, n_utt, 0, total, e->h_slot, e->h_role, ts_us ? e->h_ts : nullptr,
-                        e->h_out, out_cap, e->h_out_offs, e->h_spans, span_cap, e->h_ctx, st);
-    else
-        rc = run_pipeline(e, e->h_text, e->h_offs, n_utt, 0, total, e->h_slot, e->h_role, ts_us ? e->h_ts : nullptr,
-                          e->h_out, out_cap, e->h_out_offs, e->h_spans, span_cap, e->h_ctx, st,
-                          x ? e->h_ext : nullptr, x ? e->h_ext_n : nullptr, x ? x->stride : 0);
-    if (rc) return rc;
+    if (h.ext) with_ext(d, e->h_ext, e->h_ext_n, h.ext_stride);
+    if ((rc = window ? run_window(e, d) : run_pipeline(e, d))) return rc;
     uint64_t tot[3];
     rc = pii_sync(e, tot);
     if (rc == PII_E_CAPACITY) {
-        HIPCHK(hipMemcpy(out_offsets, e->h_out_offs, (n_utt + 1) * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h.out_offs, e->h_out_offs, (n_utt + 1) * 8, hipMemcpyDeviceToHost));
         if (n_spans) *n_spans = (uint32_t)tot[1];
         return rc;
     }
     if (rc) return rc;
-    HIPCHK(hipMemcpy(out_offsets, e->h_out_offs, (n_utt + 1) * 8, hipMemcpyDeviceToHost));
-    if (tot[0]) HIPCHK(hipMemcpy(out_bytes, e->h_out, tot[0], hipMemcpyDeviceToHost));
-    if (tot[1]) HIPCHK(hipMemcpy(spans, e->h_spans, tot[1] * sizeof(pii_span), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.out_offs, e->h_out_offs, (n_utt + 1) * 8, hipMemcpyDeviceToHost));
+    if (tot[0]) HIPCHK(hipMemcpy(h.out, e->h_out, tot[0], hipMemcpyDeviceToHost));
+    if (tot[1]) HIPCHK(hipMemcpy(h.spans, e->h_spans, tot[1] * sizeof(pii_span), hipMemcpyDeviceToHost));
     if (n_spans) *n_spans = (uint32_t)tot[1];
-    if (ctx_info && n_utt) HIPCHK(hipMemcpy(ctx_info, e->h_ctx, n_utt * 2, hipMemcpyDeviceToHost));
+    if (h.ctx_info && n_utt) HIPCHK(hipMemcpy(h.ctx_info, e->h_ctx, n_utt * 2, hipMemcpyDeviceToHost));
     return PII_OK;
 }
 
 // pii_context_update: stage the rows as host_call does, run the context-only pipeline, copy ctx_info back
-int host_context(pii_engine* e, const uint8_t* bytes, const uint64_t* offsets, uint32_t n_utt,
-                 const uint32_t* conv_slot, const uint8_t* role, const int64_t* ts_us, int16_t* ctx_info) {
-    if (!e || !offsets || (n_utt && (!conv_slot || !role))) return PII_E_ARG;
-    for (uint32_t i = 0; i < n_utt; ++i)
-        if (offsets[i + 1] < offsets[i]) return PII_E_ARG;
-    HIPCHK(hipSetDevice(e->device));
-    const uint64_t base = offsets[0], total = offsets[n_utt] - base;
-    int rc;
-    if (total + 16 > e->cap_h_bytes) {
-        const uint64_t nb = total + total / 8 + 64;
-        if ((rc = grow(e, e->h_text, nb))) return rc;
-        e->cap_h_bytes = nb;
-    }
-    if (n_utt + 1 > e->cap_h_utt) {
-        const uint32_t nu = n_utt + n_utt / 8 + 64;
-        if ((rc = grow(e, e->h_offs, nu + 1)) || (rc = grow(e, e->h_out_offs, nu + 1)) ||
-            (rc = grow(e, e->h_slot, nu)) || (rc = grow(e, e->h_role, nu)) || (rc = grow(e, e->h_ts, nu)) ||
-            (rc = grow(e, e->h_ctx, nu)))
-            return rc;
-        e->cap_h_utt = nu;
-    }
-    hipStream_t st = e->stream;
-    std::vector<uint64_t> rel(n_utt + 1);
-    for (uint32_t i = 0; i <= n_utt; ++i) rel[i] = offsets[i] - base;
-    if (total) HIPCHK(hipMemcpyAsync(e->h_text, bytes + base, total, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(e->h_offs, rel.data(), (n_utt + 1) * 8, hipMemcpyHostToDevice, st));
-    if (n_utt) {
-        HIPCHK(hipMemcpyAsync(e->h_slot, conv_slot, n_utt * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(e->h_role, role, n_utt, hipMemcpyHostToDevice, st));
-        if (ts_us) HIPCHK(hipMemcpyAsync(e->h_ts, ts_us, n_utt * 8, hipMemcpyHostToDevice, st));
-    }
-    if ((rc = run_context(e, e->h_text, e->h_offs, n_utt, total, e->h_slot, e->h_role, ts_us ? e->h_ts : nullptr,
-                          e->h_ctx, st)))
-        return rc;
-    if ((rc = pii_sync(e, nullptr))) return rc;
-    if (ctx_info && n_utt) HIPCHK(hipMemcpy(ctx_info, e->h_ctx, n_utt * 2, hipMemcpyDeviceToHost));
+int host_context(pii_engine* e, const Call& h) {
+    if (!e) return PII_E_ARG;
+    Call d;
+    int rc = stage_rows(e, h, d);
+    if (rc || (rc = run_context(e, d)) || (rc = pii_sync(e, nullptr))) return rc;
+    if (h.ctx_info && h.n_utt) HIPCHK(hipMemcpy(h.ctx_info, e->h_ctx, h.n_utt * 2, hipMemcpyDeviceToHost));
     return PII_OK;
 }
 
-int device_call(pii_engine* e, bool window, const uint8_t* d_bytes, const uint64_t* d_offsets, uint32_t n_utt,
-                const uint32_t* d_slot, const uint8_t* d_role, const int64_t* d_ts, uint8_t* d_out, uint64_t out_cap,
-                uint64_t* d_out_offsets, pii_span* d_spans, uint32_t span_cap, int16_t* d_ctx_info, void* stream,
-                const uint64_t* declared, const ExtArgs* x) {
-    if (!e || !d_offsets || !d_slot || !d_role || !d_out_offsets) return PII_E_ARG;
-    if (n_utt > 0 && (!d_bytes || !d_out || !d_spans)) return PII_E_ARG;
+// device-buffer calls: the batch's base and size come declared, or from one host round trip
+int device_call(pii_engine* e, bool window, Call c, void* stream, const uint64_t* declared) {
+    if (!e || !c.offs || !c.slot || !c.role || !c.out_offs) return PII_E_ARG;
+    if (c.n_utt > 0 && (!c.text || !c.out || !c.spans)) return PII_E_ARG;
     HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    c.st = stream ? static_cast<hipStream_t>(stream) : e->stream;
     uint64_t tb[2] = {0, 0};
     if (declared) {          // the caller states offsets[0] and the batch size: no host round trip
         tb[0] = declared[0];
         tb[1] = declared[0] + declared[1];
     } else {
-        HIPCHK(hipMemcpyAsync(tb, d_offsets, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(tb + 1, d_offsets + n_utt, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyAsync(tb, c.offs, 8, hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipMemcpyAsync(tb + 1, c.offs + c.n_utt, 8, hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipStreamSynchronize(c.st));
     }
     if (tb[1] < tb[0]) return PII_E_ARG;
-    if (window)
-        return run_window(e, d_bytes, d_offsets, n_utt, tb[0], tb[1] - tb[0], d_slot, d_role, d_ts, d_out, out_cap,
-                          d_out_offsets, d_spans, span_cap, d_ctx_info, st);
-    return run_pipeline(e, d_bytes, d_offsets, n_utt, tb[0], tb[1] - tb[0], d_slot, d_role, d_ts, d_out, out_cap,
-                        d_out_offsets, d_spans, span_cap, d_ctx_info, st, x ? x->ext : nullptr, x ? x->ext_n : nullptr,
-                        x ? x->stride : 0);
+    c.base = tb[0];
+    c.total = tb[1] - tb[0];
+    return window ? run_window(e, c) : run_pipeline(e, c);
 }
 }  // namespace
 
@@ -7001,22 +6399,25 @@ int pii_scan_redact(pii_engine* e, const uint8_t* bytes, const uint64_t* offsets
                     const uint32_t* conv_slot, const uint8_t* role, const int64_t* ts_us, uint8_t* out_bytes,
                     uint64_t out_cap, uint64_t* out_offsets, pii_span* spans, uint32_t span_cap, uint32_t* n_spans,
                     int16_t* ctx_info) {
-    return host_call(e, false, bytes, offsets, n_utt, conv_slot, role, ts_us, out_bytes, out_cap, out_offsets, spans,
-                     span_cap, n_spans, ctx_info);
+    Call c = call_rows(bytes, offsets, n_utt, conv_slot, role, ts_us);
+    return host_call(e, false, with_out(c, out_bytes, out_cap, out_offsets, spans, span_cap, ctx_info), n_spans);
 }
 
 int pii_context_update(pii_engine* e, const uint8_t* bytes, const uint64_t* offsets, uint32_t n_utt,
                        const uint32_t* conv_slot, const uint8_t* role, const int64_t* ts_us, int16_t* ctx_info) {
-    return host_context(e, bytes, offsets, n_utt, conv_slot, role, ts_us, ctx_info);
+    Call c = call_rows(bytes, offsets, n_utt, conv_slot, role, ts_us);
+    c.ctx_info = ctx_info;
+    return host_context(e, c);
 }
 
 int pii_scan_redact_ext(pii_engine* e, const uint8_t* bytes, const uint64_t* offsets, uint32_t n_utt,
                         const uint32_t* conv_slot, const uint8_t* role, const int64_t* ts_us, uint8_t* out_bytes,
                         uint64_t out_cap, uint64_t* out_offsets, pii_span* spans, uint32_t span_cap, uint32_t* n_spans,
                         int16_t* ctx_info, const pii_span* ext, const uint32_t* ext_n, uint32_t ext_stride) {
-    const ExtArgs x{ext, ext_n, ext_stride};
-    return host_call(e, false, bytes, offsets, n_utt, conv_slot, role, ts_us, out_bytes, out_cap, out_offsets, spans,
-                     span_cap, n_spans, ctx_info, &x);
+    if (!ext || !ext_n || ext_stride == 0) return PII_E_ARG;
+    Call c = call_rows(bytes, offsets, n_utt, conv_slot, role, ts_us);
+    with_ext(c, ext, ext_n, ext_stride);
+    return host_call(e, false, with_out(c, out_bytes, out_cap, out_offsets, spans, span_cap, ctx_info), n_spans);
 }
 
 int pii_scan_redact_device_ext(pii_engine* e, const uint8_t* d_bytes, const uint64_t* d_offsets, uint32_t n_utt,
@@ -7026,9 +6427,9 @@ int pii_scan_redact_device_ext(pii_engine* e, const uint8_t* d_bytes, const uint
                                const uint32_t* d_ext_n, uint32_t ext_stride, void* stream) {
     if (!d_ext || !d_ext_n || ext_stride == 0) return PII_E_ARG;
     const uint64_t decl[2] = {batch_base, batch_bytes};
-    const ExtArgs x{d_ext, d_ext_n, ext_stride};
-    return device_call(e, false, d_bytes, d_offsets, n_utt, d_slot, d_role, d_ts, d_out, out_cap, d_out_offsets,
-                       d_spans, span_cap, d_ctx_info, stream, decl, &x);
+    Call c = call_rows(d_bytes, d_offsets, n_utt, d_slot, d_role, d_ts);
+    with_ext(c, d_ext, d_ext_n, ext_stride);
+    return device_call(e, false, with_out(c, d_out, out_cap, d_out_offsets, d_spans, span_cap, d_ctx_info), stream, decl);
 }
 
 int pii_window_enable_ex(pii_engine* e, uint32_t window_n, uint32_t slot_bytes, uint32_t flags) {
@@ -7044,11 +6445,8 @@ int pii_window_enable_ex(pii_engine* e, uint32_t window_n, uint32_t slot_bytes, 
     WinTables w;
     int rc = alloc_window_tables(e, w, ns, window_n, slot_bytes);
     if (rc) return rc;
-    free_window_tables(e);
-    e->wr_desc = w.desc;
-    e->wr_cnt = w.cnt;
-    e->wr_head = w.head;
-    e->wr_arena = w.arena;
+    free_window_tables(e->wr);
+    e->wr = w;
     // the incremental path needs no detector that consumes '\n' or tests a text edge (a match inside a
     // window is then its utterance's own match); it takes any number of patterns and SCAN groups
     // (config 5: the groups' merged pair queue, candidate lists past LIVE patterns spilled like
@@ -7096,18 +6494,13 @@ int pii_context_resize(pii_engine* e, uint32_t n_conv_slots) {
               hipMemset(s + old, 0, (ns - old) * 4) == hipSuccess;
     if (ok && e->win_n) {
         const size_t N = e->win_n, sb = e->win_slot_bytes;
-        ok = hipMemcpy(w.desc, e->wr_desc, old * N * sizeof(WDesc), hipMemcpyDeviceToDevice) == hipSuccess &&
-             hipMemcpy(w.cnt, e->wr_cnt, old * 4, hipMemcpyDeviceToDevice) == hipSuccess &&
-             hipMemcpy(w.head, e->wr_head, old * 4, hipMemcpyDeviceToDevice) == hipSuccess &&
-             hipMemcpy(w.arena, e->wr_arena, old * sb, hipMemcpyDeviceToDevice) == hipSuccess;
+        ok = hipMemcpy(w.desc, e->wr.desc, old * N * sizeof(WDesc), hipMemcpyDeviceToDevice) == hipSuccess &&
+             hipMemcpy(w.cnt, e->wr.cnt, old * 4, hipMemcpyDeviceToDevice) == hipSuccess &&
+             hipMemcpy(w.head, e->wr.head, old * 4, hipMemcpyDeviceToDevice) == hipSuccess &&
+             hipMemcpy(w.arena, e->wr.arena, old * sb, hipMemcpyDeviceToDevice) == hipSuccess;
     }
     if (!ok) {
-        if (e->win_n) {
-            (void)hipFree(w.desc);
-            (void)hipFree(w.cnt);
-            (void)hipFree(w.head);
-            (void)hipFree(w.arena);
-        }
+        free_window_tables(w);
         return undo(PII_E_DEVICE);
     }
     (void)hipFree(e->st_group);
@@ -7117,11 +6510,8 @@ int pii_context_resize(pii_engine* e, uint32_t n_conv_slots) {
     e->st_ts = t;
     e->stamp = s;
     if (e->win_n) {
-        free_window_tables(e);
-        e->wr_desc = w.desc;
-        e->wr_cnt = w.cnt;
-        e->wr_head = w.head;
-        e->wr_arena = w.arena;
+        free_window_tables(e->wr);
+        e->wr = w;
     }
     e->n_slots = n_conv_slots;
     return PII_OK;
@@ -7153,7 +6543,7 @@ int pii_window_reset(pii_engine* e, uint32_t slot) {
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     const uint32_t z = 0;
-    HIPCHK(hipMemcpy(e->wr_cnt + slot, &z, 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->wr.cnt + slot, &z, 4, hipMemcpyHostToDevice));
     return PII_OK;
 }
 
@@ -7161,7 +6551,7 @@ int pii_window_count(pii_engine* e, uint32_t slot, uint32_t* n_entries) {
     if (!e || e->win_n == 0 || slot >= e->n_slots || !n_entries) return PII_E_ARG;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(n_entries, e->wr_cnt + slot, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(n_entries, e->wr.cnt + slot, 4, hipMemcpyDeviceToHost));
     return PII_OK;
 }
 
@@ -7169,16 +6559,17 @@ int pii_rescan_window(pii_engine* e, const uint8_t* bytes, const uint64_t* offse
                       const uint32_t* conv_slot, const uint8_t* role, const int64_t* ts_us, uint8_t* out_bytes,
                       uint64_t out_cap, uint64_t* out_offsets, pii_span* spans, uint32_t span_cap, uint32_t* n_spans,
                       int16_t* win_ctx) {
-    return host_call(e, true, bytes, offsets, n_utt, conv_slot, role, ts_us, out_bytes, out_cap, out_offsets, spans,
-                     span_cap, n_spans, win_ctx);
+    Call c = call_rows(bytes, offsets, n_utt, conv_slot, role, ts_us);
+    return host_call(e, true, with_out(c, out_bytes, out_cap, out_offsets, spans, span_cap, win_ctx), n_spans);
 }
 
 int pii_rescan_window_device(pii_engine* e, const uint8_t* d_bytes, const uint64_t* d_offsets, uint32_t n_utt,
                              const uint32_t* d_conv_slot, const uint8_t* d_role, const int64_t* d_ts_us,
                              uint8_t* d_out_bytes, uint64_t out_cap, uint64_t* d_out_offsets, pii_span* d_spans,
                              uint32_t span_cap, int16_t* d_win_ctx, void* stream) {
-    return device_call(e, true, d_bytes, d_offsets, n_utt, d_conv_slot, d_role, d_ts_us, d_out_bytes, out_cap,
-                       d_out_offsets, d_spans, span_cap, d_win_ctx, stream, nullptr);
+    Call c = call_rows(d_bytes, d_offsets, n_utt, d_conv_slot, d_role, d_ts_us);
+    return device_call(e, true, with_out(c, d_out_bytes, out_cap, d_out_offsets, d_spans, span_cap, d_win_ctx), stream,
+                       nullptr);
 }
 
 int pii_rescan_window_device_ex(pii_engine* e, const uint8_t* d_bytes, const uint64_t* d_offsets, uint32_t n_utt,
@@ -7187,8 +6578,9 @@ int pii_rescan_window_device_ex(pii_engine* e, const uint8_t* d_bytes, const uin
                                 uint64_t* d_out_offsets, pii_span* d_spans, uint32_t span_cap, int16_t* d_win_ctx,
                                 void* stream) {
     const uint64_t decl[2] = {batch_base, batch_bytes};
-    return device_call(e, true, d_bytes, d_offsets, n_utt, d_conv_slot, d_role, d_ts_us, d_out_bytes, out_cap,
-                       d_out_offsets, d_spans, span_cap, d_win_ctx, stream, decl);
+    Call c = call_rows(d_bytes, d_offsets, n_utt, d_conv_slot, d_role, d_ts_us);
+    return device_call(e, true, with_out(c, d_out_bytes, out_cap, d_out_offsets, d_spans, span_cap, d_win_ctx), stream,
+                       decl);
 }
 
 int pii_context_get(pii_engine* e, uint32_t slot, int32_t* group, int64_t* ts_us) {

@@ -46,3 +46,39 @@ def test_no_cpu_fallback_without_gpu(compiled):
     with pytest.raises(E.PiiError) as ei:
         E.Engine(compiled.blob, device=0, n_conv_slots=4)
     assert ei.value.code == E.PII_E_DEVICE
+
+
+# ---- the host rule preparation runs before the first HIP call: a malformed blob is PII_E_RULES on a
+# machine without a usable device, a well-formed one gets as far as the device
+@pytest.fixture(scope="module")
+def hash_compiled():
+    import blob_damage
+    return blob_damage.hash_config_compiled()
+
+
+def _create(blob: bytes) -> int:
+    E = pkg("engine")
+    lib = E.load_library()
+    h = ctypes.c_void_p()
+    rc = lib.pii_engine_create(blob, len(blob), 0, 4, 0, ctypes.byref(h))
+    if rc == 0:
+        lib.pii_engine_destroy(h)
+    return rc
+
+
+def _damage_params():
+    import blob_damage
+    return pytest.mark.parametrize("damage", blob_damage.ALL_DAMAGE, ids=blob_damage.damage_id)
+
+
+@_damage_params()
+def test_damaged_blob_is_rejected_before_the_device(damage, hash_compiled):
+    import blob_damage
+    assert _create(blob_damage.damaged_blob(hash_compiled, damage)) == pkg("engine").PII_E_RULES
+
+
+def test_undamaged_hash_blob_reaches_the_device(hash_compiled):
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    assert _create(hash_compiled.blob) == pkg("engine").PII_E_DEVICE

@@ -11,6 +11,8 @@ import pytest
 
 import xform_configs as X
 import xform_hash_ref as HR
+from blob_damage import (_hash_key_dropped, _hash_mid_dropped, _key_index_out_of_range, _key_table_short,
+                         _mid_cut_short, _placeholder_short)
 from conftest import pkg
 
 pytestmark = pytest.mark.gpu
@@ -347,34 +349,6 @@ def test_window_rescan_takes_the_full_path(cfgs, oracle_cfg):
 
 
 # -------------------------------------------------------------------------------- 8 malformed blobs
-def _hash_mid_dropped(S):
-    del S["xf.hash_mid"]
-
-
-def _hash_key_dropped(S):
-    del S["xf.hash_key"]
-
-
-def _key_index_out_of_range(S, names):
-    S["xf.hash_key"] = S["xf.hash_key"].copy()
-    S["xf.hash_key"][names.index("PHONE_NUMBER")] = 2                # two keys: 0 and 1
-
-
-def _mid_cut_short(S):
-    S["xf.hash_mid"] = S["xf.hash_mid"][:24].copy()
-
-
-def _key_table_short(S):
-    S["xf.hash_key"] = S["xf.hash_key"][:-1].copy()
-
-
-def _placeholder_short(S, names):
-    off = S["xf.repl_off"].copy()
-    t = names.index("PHONE_NUMBER")
-    off[t + 1:] -= 1                                                   # 43 bytes for one hash type
-    S["xf.repl_off"] = off
-
-
 @pytest.mark.parametrize("damage", [_hash_mid_dropped, _hash_key_dropped, _key_index_out_of_range, _mid_cut_short,
                                     _key_table_short, _placeholder_short], ids=lambda f: f.__name__.strip("_"))
 def test_malformed_hash_sections_are_rejected(damage, cfgs):

@@ -320,3 +320,31 @@ def test_many_cut_rows_closed_gate(eng, ref, oracle_cfg):
     assert n_cut > 30 and len(rows) > 1024
     _, st = _check(eng, ref, rows, oracle_cfg)
     assert (st["cut_rows"], st["long_kernels_launched"], st["reruns"]) == (n_cut, 1, 1)
+
+
+# ------------------------------------------------ 8. the re-run keeps the call's external candidates
+def test_rerun_carries_external_candidates(eng, oracle_cfg):
+    """a closed-gate call with a cut row and a row with two external spans: pii_sync's re-run is the
+    same call, external candidates included (output, spans and histogram as the oracle's with them)"""
+    from oracle import pii_oracle as O
+    P = oracle_cfg.type_id["PERSON_NAME"]
+    rows, n_cut = _edge_rows("first_row", random.Random(8), _slots(8))
+    assert len(rows) == 3 and all(x == O.ROLE_CUSTOMER for _, x, _, _ in rows)
+    assert rows[1][2] == b"reach me at jane.doe@example.com please"
+    ext = [[], [(0, 5, P, 4), (33, 39, P, 5)], []]                     # "reach", "please"
+    eng.histogram_reset()
+    res = eng.scan_redact([t for _, _, t, _ in rows], [c for c, _, _, _ in rows], [x for _, x, _, _ in rows],
+                          [s for _, _, _, s in rows], ext=ext)
+    st = eng.stats(gate=True)
+    assert st["lane_bytes"] == LANE
+    assert (st["cut_rows"], st["long_kernels_launched"], st["reruns"]) == (n_cut, 1, 1)
+    hist = eng.histogram()
+    ohist = np.zeros(len(hist), dtype=np.uint64)
+    exp = O.process_rows(rows, oracle_cfg, extra=ext)
+    for i, (red, fs, _, _) in enumerate(exp):
+        assert res.text(i) == red, (i, res.text(i)[:80], red[:80])
+        assert _spans(res, i) == [(f.start, f.end, f.type_id, f.likelihood) for f in fs], i
+        for f in fs:
+            ohist[f.type_id] += 1
+    assert [(f.start, f.end) for f in exp[1][1] if f.type_id == P] == [(0, 5), (33, 39)]
+    assert np.array_equal(hist, ohist)
