@@ -1235,6 +1235,14 @@ SCAN_WIDE_BYTES = 124 * 1024    # a WIDE group >= 1 (engine: rows padded to 4 en
                                 # one workgroup per CU): up to 64k transitions
 SPILL_PREFIX = 10               # prefix of the built-ins moved out of group 0 (plan_scan_groups)
 SCAN_GROUPS_MAX = 8             # k_pairs_merge merges at most this many per-group event lists per lane
+# Exclusion rules (mirrors of csrc/pii_layout.h).  A rule set whose exclusions k_select can decide while it
+# streams a lane (FULL_MATCH only, at most NE_MAX excluder patterns, no type both excluded and excluding)
+# compiles to var.excl_* / det.exidx; any other is GENERAL: those stay empty and k_exclude reads var.xg_* /
+# det.xgidx instead.
+NE_MAX = 2                      # excluder patterns of the streaming form
+NX_MAX = 64                     # excluder patterns of a general rule set
+XG_PARTIAL = 0x8000             # var.xg_ids entry: excluder type id | this bit for MATCHING_TYPE_PARTIAL_MATCH
+MATCHING_TYPES = ("MATCHING_TYPE_FULL_MATCH", "MATCHING_TYPE_PARTIAL_MATCH")
 DICT_SCAN_PREFIX = 4            # SCAN prefix of dictionary infoTypes (Rules)
 
 
@@ -1436,16 +1444,22 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
                             per_type_rules[rules.type_id[tn]].append(hot_index[key])
                 elif "exclusion_rule" in rule:
                     ex = rule["exclusion_rule"]
+                    if "exclude_info_types" not in ex:
+                        form = next((k for k in ("regex", "dictionary", "exclude_by_hotword") if k in ex), None)
+                        raise RuleError(f"exclusion_rule.{form} is not supported (only exclude_info_types)" if form
+                                        else "exclusion_rule without exclude_info_types")
                     mt = ex.get("matching_type", "MATCHING_TYPE_FULL_MATCH")
-                    if mt != "MATCHING_TYPE_FULL_MATCH" or "exclude_info_types" not in ex:
-                        raise RuleError("only exclude_info_types with MATCHING_TYPE_FULL_MATCH is supported")
+                    if mt not in MATCHING_TYPES:
+                        raise RuleError(f"exclusion_rule: unknown matching_type {mt}")
+                    partial = XG_PARTIAL if mt == "MATCHING_TYPE_PARTIAL_MATCH" else 0
                     xs = [it["name"] for it in ex["exclude_info_types"].get("info_types", [])]
                     for tn in tnames:
                         if tn in rules.type_id:
-                            per_type_excl[rules.type_id[tn]].extend(rules.type_id[x] for x in xs if x in rules.type_id)
+                            per_type_excl[rules.type_id[tn]].extend(rules.type_id[x] | partial
+                                                                    for x in xs if x in rules.type_id)
         for x in rules.external_types:
             xt = rules.type_id[x]
-            if per_type_rules[xt] or per_type_excl[xt] or any(xt in l for l in per_type_excl):
+            if per_type_rules[xt] or per_type_excl[xt] or any(xt in [i & ~XG_PARTIAL for i in l] for l in per_type_excl):
                 raise RuleError(f"external type {x} cannot be named by a hotword or exclusion rule")
         for t in range(T):
             rule_ids.extend(per_type_rules[t])
@@ -1455,18 +1469,32 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
     # excluder patterns (their type is excluded-against in some variant) get a slot in the resolve
     # kernel's private state and come FIRST in every SCAN-D accept set, so that a same-start
     # excluder is known before the findings it may exclude (A.5).
-    excluder_types = set(excl_ids[:int(excl_off[-1])])
+    excluder_types = {i & ~XG_PARTIAL for i in excl_ids[:int(excl_off[-1])]}
     excluded_types = {t for v in range(V) for t in range(T) if excl_off[v * T + t + 1] > excl_off[v * T + t]}
-    if excluder_types & excluded_types:
-        raise RuleError("an infoType that is both excluded and excluding is not supported")
     exidx = np.full(P, 0xFF, dtype=np.uint8)
     ne = 0
     for p in rules.patterns:
         if rules.type_id[p.type_name] in excluder_types:
-            exidx[p.pid] = ne
+            exidx[p.pid] = min(ne, 0xFE)
             ne += 1
-    if ne > 8:
-        raise RuleError("more than 8 excluder patterns")
+    # GENERAL (the streaming form cannot express it): a PARTIAL_MATCH entry, more excluder patterns than
+    # k_select keeps, or a type both excluded and excluding.  The lists move to var.xg_* / det.xgidx (read
+    # by k_exclude, which marks the excluded candidates before k_select runs) and the streaming tables stay
+    # empty.
+    general = (any(i & XG_PARTIAL for i in excl_ids) or ne > NE_MAX or bool(excluder_types & excluded_types))
+    xg_sections = OrderedDict()
+    if general:
+        if ne > NX_MAX:
+            raise RuleError(f"{ne} excluder patterns (more than {NX_MAX})")
+        if T >= XG_PARTIAL:
+            raise RuleError(f"{T} info types: a general exclusion list holds type ids below {XG_PARTIAL}")
+        xg_sections["var.xg_off"] = excl_off
+        xg_sections["var.xg_ids"] = np.array(excl_ids or [0], dtype=np.uint16)
+        xg_sections["det.xgidx"] = exidx
+        excl_off = np.zeros(V * T + 1, dtype=np.uint32)
+        excl_ids = []
+        exidx = np.full(P, 0xFF, dtype=np.uint8)
+        window_ok = 0          # k_win_select's streaming exclusion cannot look ahead: windows re-scan in FULL
     # one accept-set id space over all scan groups: group g's set a > 0 -> acc_base[g] + a
     acc_sets: List[Tuple[int, ...]] = [()]
     acc_base = []
@@ -1562,6 +1590,8 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
             S[f"scan.g{g}.accid"] = global_accid(g, m)
     # deidentify_config: per-type kind, replacement strings, mask parameters (absent: "[TYPE]" for all)
     S.update(transform_sections(rules.transforms))
+    # general exclusion rules: per-(variant, type) lists with the matching bit, per-pattern excluder index
+    S.update(xg_sections)
     blob = _sections_to_blob(S)
     return Compiled(rules, scan_d, scan_k, first, hot, hot_rules, S, blob, [[p.pid for p in ps] for ps, _ in groups])
 

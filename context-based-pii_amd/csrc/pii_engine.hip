@@ -2744,6 +2744,206 @@ __global__ __launch_bounds__(ROW_BLOCK) void k_rowlen(const Geo g, const uint32_
     }
 }
 
+// ---------------------------------------------------------------------------- general exclusion
+// k_exclude: the exclusion rules k_select's streaming form cannot decide (a PARTIAL_MATCH entry, more
+// than NE_MAX excluder patterns, a type both excluded and excluding; compiler.py `general`).  Launched
+// between k_pair_eval and k_select for such rule sets only; k_select then sees empty exclusion lists
+// and an excluded candidate as one below min_likelihood (lik = -1): it still feeds its pattern's
+// finditer state and does not compete for its start, as in LaneSel::consider.
+//
+// The oracle (find_pii) drops candidate c when another candidate g of a listed type overlaps it
+// (PARTIAL_MATCH) or contains it (FULL_MATCH), over the UNFILTERED candidate list: an excluder that is
+// itself excluded, or later loses overlap resolution, still excludes.  So the pass has two phases:
+//   k_excl_occ<false/true>  per lane, the walk of k_select: the OCCURRENCES, the matched pairs of excluder
+//       patterns that are candidates -- type enabled in the row's variant, then not inside the pattern's
+//       previous match (finditer; the test order of LaneSel::pair), then likelihood >= min_likelihood.
+//       Counted per lane, placed by an exclusive scan, written in queue order = ascending start.
+//   k_excl_mark             per matched pair whose (variant, type) list is not empty: a search of the
+//       occurrences for one that excludes it; lik = -1 on a hit.
+// Positions are batch relative (row offset + row-relative position): no match crosses a row, so two
+// spans overlap only within one row and neither the per-pattern last ends nor the search compare rows.
+// Cut rows are exact: the thread of the lane a row starts in walks the row's further lanes itself, with
+// the state it carries; a continuation lane's own thread skips the continued row's pairs.  (A 64 MB
+// row is one thread's serial walk over all of the row's matched pairs.)
+struct XOcc {              // one occurrence (16 B)
+    uint32_t s, e;         // [s, e), batch relative
+    uint32_t p;            // detector pattern
+    uint32_t mx;           // largest end among the occurrences its writer's walk met up to this one
+};
+struct ExclTabs {          // k_exclude's own tables (in the rules buffer)
+    const uint32_t* xoff;  // [V*T+1] per (variant, type): its exclusion list in xids
+    const uint16_t* xids;  // excluder type | XG_PARTIAL
+    const uint8_t* xidx;   // [P] excluder pattern -> index < nx, or 0xff
+    const uint16_t* dtype;
+    const uint8_t* ven;
+    const uint8_t* vmin;
+    int T, nx;
+};
+struct ExclIO {
+    const uint64_t* lane_pair;
+    const uint32_t* lane_np;
+    SelRec* sel;
+    const int32_t* pend;
+    uint64_t pair_cap;
+    uint32_t* xcnt;        // [2 * lanes] occurrences of lane c: in the row it continues, in the rows it starts
+    const uint64_t* xbase; // exclusive scan of xcnt; [2 * lanes] = the total
+    XOcc* occ;
+    uint64_t occ_cap;
+};
+constexpr uint32_t X_NO_ROW = 0xffffffffu;
+constexpr int EXCL_BLOCK = 256;
+
+// f(i, end) for every matched pair i (run relative) of the run [pbase, pbase + np), until it returns
+// false.  pend is read as aligned 16-byte groups, the next one issued before this one is decoded (the
+// allocation ends 16 entries past pair_cap, as for select_run).
+template <class F>
+__device__ __forceinline__ void for_matched(const int32_t* __restrict__ pend, uint64_t pbase, uint32_t np, F&& f) {
+    const uint32_t off0 = (uint32_t)(pbase & 3u);
+    const int4* pa = reinterpret_cast<const int4*>(pend + (pbase - off0));
+    const uint32_t ng = (off0 + np + 3u) >> 2;
+    int4 q = pa[0];
+    for (uint32_t gi = 0; gi < ng; ++gi) {
+        const int4 d = q;
+        if (gi + 1 < ng) q = pa[gi + 1];
+        const int32_t v[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t k = 4u * gi + j;
+            if (v[j] >= 0 && k >= off0 && k < off0 + np)
+                if (!f(k - off0, v[j])) return;
+        }
+    }
+}
+
+// one thread's walk state: the end of each excluder pattern's last match (LDS column `last`, stride
+// EXCL_BLOCK), the running largest end, the row whose offset is cached
+struct ExclWalk {
+    uint32_t* last;
+    uint32_t mx, cu, coff;
+};
+
+// the occurrences among lane `lane`'s matched pairs: those of row `only` (X_NO_ROW: of every row but
+// `skip`); WRITE: placed from occ + base on.  Returns their count.
+template <bool WRITE>
+__device__ __forceinline__ uint32_t excl_walk(const ExclTabs& X, const Geo& g, const ExclIO& io, ExclWalk& W,
+                                              uint32_t lane, uint32_t skip, uint32_t only, uint64_t base) {
+    const uint32_t np = io.lane_np[lane];
+    const uint64_t pbase = io.lane_pair[lane];
+    uint32_t n = 0;
+    if (np == 0 || pbase + np > io.pair_cap) return 0;
+    for_matched(io.pend, pbase, np, [&](uint32_t i, int32_t e) -> bool {
+        const SelRec r = io.sel[pbase + i];
+        if (only != X_NO_ROW) {
+            if (r.u != only) return false;          // the continued row's pairs come first
+        } else if (r.u == skip) {
+            return true;
+        }
+        const uint32_t p = r.p & 0xffffu, v = r.p >> 16;
+        const uint32_t xi = X.xidx[p];
+        if (xi == 0xffu) return true;
+        const uint32_t t = X.dtype[p];
+        if (!X.ven[v * (uint32_t)X.T + t]) return true;
+        if (r.u != W.cu) {
+            W.cu = r.u;
+            W.coff = (uint32_t)g_off(g, r.u);
+        }
+        const uint32_t sa = W.coff + (uint32_t)r.ps, ea = W.coff + (uint32_t)e;
+        uint32_t* le = W.last + xi * EXCL_BLOCK;
+        if (sa < *le) return true;                  // inside the pattern's previous match (finditer)
+        *le = ea;
+        if (r.lik < (int32_t)X.vmin[v]) return true;
+        W.mx = max(W.mx, ea);
+        if (WRITE) {
+            XOcc o;
+            o.s = sa;
+            o.e = ea;
+            o.p = p;
+            o.mx = W.mx;
+            io.occ[base + n] = o;
+        }
+        ++n;
+        return true;
+    });
+    return n;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(EXCL_BLOCK) void k_excl_occ(const ExclTabs X, const Geo g, const ExclIO io,
+                                                        uint32_t* __restrict__ err) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_last[];      // [nx][EXCL_BLOCK]
+    if (*err & ERR_ABORT) return;
+    const uint64_t total = WRITE ? io.xbase[2ull * g.n_chunks] : 0;
+    if (WRITE && total > io.occ_cap) {              // the occurrence list is too short: pii_sync re-runs the call
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err, (uint32_t)ERR_QUEUE);
+        return;
+    }
+    const uint32_t c = blockIdx.x * EXCL_BLOCK + threadIdx.x;
+    if (c >= g.n_chunks) return;
+    ExclWalk W{s_last + threadIdx.x, 0u, X_NO_ROW, 0u};
+    for (int x = 0; x < X.nx; ++x) W.last[x * EXCL_BLOCK] = 0u;
+    Lane L = g_lane(g, c);
+    const uint32_t n_own = excl_walk<WRITE>(X, g, io, W, c, L.clo ? L.u0 : X_NO_ROW, X_NO_ROW,
+                                            WRITE ? io.xbase[2ull * c + 1] : 0);
+    if (!WRITE) {
+        io.xcnt[2ull * c + 1] = n_own;
+        if (!L.clo) io.xcnt[2ull * c] = 0u;
+    }
+    // the row cut at the lane's end, if it starts in this lane: its further lanes, with the state carried
+    // (a lane inside the row leaves them to the thread of the row's first lane)
+    uint32_t lane = c;
+    if (L.clo && L.u0 == L.u1 - 1) return;
+    while (L.chi && lane + 1 < g.n_chunks) {
+        const uint32_t r = L.u1 - 1;
+        ++lane;
+        L = g_lane(g, lane);
+        if (!L.clo || L.u0 != r) break;
+        const uint32_t n = excl_walk<WRITE>(X, g, io, W, lane, X_NO_ROW, r, WRITE ? io.xbase[2ull * lane] : 0);
+        if (!WRITE) io.xcnt[2ull * lane] = n;
+        if (L.u1 - 1 != r) break;                   // the row ends in this lane
+    }
+}
+
+__global__ __launch_bounds__(256) void k_excl_mark(const ExclTabs X, const Geo g, const ExclIO io,
+                                                   const unsigned long long* __restrict__ pair_count,
+                                                   const uint32_t* __restrict__ err) {
+    if (*err & ERR_ABORT) return;
+    const uint64_t nocc = io.xbase[2ull * g.n_chunks];
+    if (nocc == 0 || nocc > io.occ_cap) return;
+    const uint64_t n = min((uint64_t)*pair_count, io.pair_cap);
+    const uint4* __restrict__ occ = reinterpret_cast<const uint4*>(io.occ);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const int32_t e = io.pend[i];
+        if (e < 0) continue;
+        const SelRec r = io.sel[i];
+        const uint32_t p = r.p & 0xffffu, v = r.p >> 16;
+        const uint32_t key = v * (uint32_t)X.T + X.dtype[p];
+        const uint32_t q0 = X.xoff[key], q1 = X.xoff[key + 1];
+        if (q0 == q1) continue;
+        const uint32_t off = (uint32_t)g_off(g, r.u);
+        const uint32_t cs = off + (uint32_t)r.ps, ce = off + (uint32_t)e;
+        // the occurrences that start before the candidate's end, latest first, down to the one from which on
+        // no earlier one reaches past the candidate's start
+        uint64_t lo = 0, hi = nocc;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (occ[mid].x < ce) lo = mid + 1;
+            else hi = mid;
+        }
+        bool hit = false;
+        for (uint64_t k = lo; k > 0 && !hit; --k) {
+            const uint4 o = occ[k - 1];             // s, e, p, mx
+            if (o.w <= cs) break;
+            if (o.y <= cs || (o.x == cs && o.z == p)) continue;      // ends before it; the candidate itself
+            const uint32_t tg = X.dtype[o.z];
+            for (uint32_t q = q0; q < q1; ++q) {
+                const uint32_t id = X.xids[q];
+                if ((id & (XG_PARTIAL - 1u)) == tg && ((id & XG_PARTIAL) || (o.x <= cs && ce <= o.y))) hit = true;
+            }
+        }
+        if (hit) io.sel[i].lik = -1;
+    }
+}
+
 // ---------------------------------------------------------------------------- exclusive scans
 __device__ __forceinline__ uint64_t wave_incl_scan(uint64_t x, int lane) {
     for (int d = 1; d < 64; d <<= 1) {
@@ -4939,6 +5139,15 @@ struct pii_engine {
     uint8_t* dirty = nullptr;
     uint64_t* lane_sp = nullptr;       // exclusive scan of lane_nf (span offsets); [lanes] = total spans
     uint2* spill = nullptr;            // k_select's per-run (pattern, end) lists, indexed like the pair queue
+    // general exclusion rules (k_exclude; pii_exclusion_mode): its tables, the per-lane occurrence counts
+    // and their scan (with the lane arrays), the occurrence list (with the queues)
+    bool excl_general = false;
+    ExclTabs xt{};
+    uint32_t* xcnt = nullptr;
+    uint64_t* xbase = nullptr;
+    XOcc* xocc = nullptr;
+    uint64_t xocc_cap = 0;
+    bool excl_ran = false;             // the last call launched k_exclude: xbase holds its occurrence count
     RSpan* rsp = nullptr;
     uint64_t cap_rsp = 0;
     uint32_t* tile_first = nullptr;
@@ -5039,6 +5248,7 @@ int ensure_scratch(pii_engine* e, uint32_t n_utt, uint64_t bytes, uint32_t n_lan
         if ((rc = grow(e, e->lane_rowbase, nl))) return rc;
         if ((rc = grow(e, e->dirty, nl))) return rc;
         if ((rc = grow(e, e->lane_sp, nl + 1))) return rc;
+        if (e->excl_general && ((rc = grow(e, e->xcnt, 2 * nl)) || (rc = grow(e, e->xbase, 2 * nl + 1)))) return rc;
         if ((rc = grow(e, e->hist_part, (nl / 256 + 2) * (size_t)std::max<uint32_t>(e->hist_types, 1)))) return rc;
         e->cap_lanes = nl;
         e->cap_bsum = 0;
@@ -5159,6 +5369,13 @@ int ensure_queues(pii_engine* e, uint64_t total_bytes) {
         if ((rc = grow(e, e->evloc, cap))) return rc;
         e->ev_cap = cap;
     }
+    // k_exclude's occurrence list: excluder matches are a small share of the pairs (an allow-list entry
+    // per few hundred bytes), so it is sized by the bytes, not by the pair queue; an overflow is ERR_QUEUE
+    if (e->excl_general && e->xocc_cap < total_bytes / 64 + 4096) {
+        const uint64_t cap = total_bytes / 64 + 4096;
+        if ((rc = grow(e, e->xocc, cap))) return rc;
+        e->xocc_cap = cap;
+    }
     return PII_OK;
 }
 
@@ -5234,6 +5451,7 @@ int begin_call(pii_engine* e, const Call& c, const CallPlan& p, CallGeo& cg) {
     e->long_min = p.cut_lanes ? p.cut_lanes << e->lane_shift : NO_CUTS;
     cg.n_chunks = lane_count(e, c.total);
     e->last_lanes = cg.n_chunks;
+    e->excl_ran = false;
     int rc = ensure_scratch(e, c.n_utt, c.total, cg.n_chunks, p.min_len);
     if (rc || ((p.ensure & ENS_QUEUES) && (rc = ensure_queues(e, c.total))) ||
         ((p.ensure & ENS_REDACT) && (rc = ensure_redact(e, c.span_cap, c.out_cap))) ||
@@ -5426,6 +5644,26 @@ struct WinFull {
     uint32_t n_new;
 };
 
+// k_exclude (general exclusion rules only): count the occurrences per lane, place them, write them, mark
+// the excluded candidates -- after k_pair_eval wrote the likelihoods, before k_select reads them
+int launch_exclude(pii_engine* e, const Call& c, const CallGeo& cg) {
+    const uint32_t n_chunks = cg.n_chunks;
+    const ExclIO io{e->lane_pair, e->lane_np, reinterpret_cast<SelRec*>(e->cont), e->pend, e->pair_cap,
+                    e->xcnt,      e->xbase,   e->xocc,                            e->xocc_cap};
+    const size_t lds = (size_t)e->xt.nx * EXCL_BLOCK * sizeof(uint32_t);
+    const uint32_t nb = (n_chunks + EXCL_BLOCK - 1) / EXCL_BLOCK;
+    HIPCHK(hipMemsetAsync(e->xcnt, 0, 2 * (size_t)n_chunks * sizeof(uint32_t), c.st));
+    k_excl_occ<false><<<nb, EXCL_BLOCK, lds, c.st>>>(e->xt, cg.g, io, e->d_err);
+    int rc = exclusive_scan(e, e->xcnt, 2 * n_chunks, e->xbase, c.st);
+    if (rc) return rc;
+    k_excl_occ<true><<<nb, EXCL_BLOCK, lds, c.st>>>(e->xt, cg.g, io, e->d_err);
+    const uint32_t nm = (uint32_t)std::min<uint64_t>((e->pair_cap + 255) / 256, 8ull * e->n_cu);
+    k_excl_mark<<<nm, 256, 0, c.st>>>(e->xt, cg.g, io, cg.pcount, e->d_err);
+    HIPCHK(hipGetLastError());
+    e->excl_ran = true;
+    return PII_OK;
+}
+
 // pii_scan_redact*: the whole pipeline.  wf: as the second pass of a full window re-scan (a window call
 // keeps its own record for pii_sync's re-run).
 int run_pipeline(pii_engine* e, const Call& c, const WinFull* wf = nullptr) {
@@ -5468,6 +5706,7 @@ int run_pipeline(pii_engine* e, const Call& c, const WinFull* wf = nullptr) {
                 e->mcount, e->n_seg, e->evloc, e->pend, e->pres, reinterpret_cast<SelRec*>(e->cont), nullptr, nullptr,
                 e->k.eval_split);
         }
+        if (e->excl_general && (rc = launch_exclude(e, c, cg))) return rc;
         const bool xg = e->img_sel_rg.d != nullptr;
         const DevImage& isel = xg ? e->img_sel_rg : e->img_sel;
         const SelIO io{e->lane_pair, e->lane_np, reinterpret_cast<const SelRec*>(e->cont), e->pend, e->pair_cap, c.role, ctx, e->fd,
@@ -5871,6 +6110,17 @@ bool upload_rules(pii_engine* e, HostRules& H) {
         set(e->d_hash_key, H.off[TB_HASH_KEY]);
         set(e->d_hash_mid, H.off[TB_HASH_MID]);
     }
+    e->excl_general = H.excl_general;
+    if (H.excl_general) {
+        set(e->xt.xoff, H.off[TB_XG_OFF]);
+        set(e->xt.xids, H.off[TB_XG_IDS]);
+        set(e->xt.xidx, H.off[TB_XG_IDX]);
+        e->xt.dtype = R.det_type;
+        e->xt.ven = R.var_enabled;
+        e->xt.vmin = R.var_minlik;
+        e->xt.T = R.T;
+        e->xt.nx = H.excl_nx;
+    }
     // SCAN groups: sg[0] = R; a group >= 1 has its own D tables and a 1-row K stub
     e->scan_lds = H.scan_lds;
     e->n_sg = 1 + (uint32_t)H.groups.size();
@@ -6169,6 +6419,14 @@ int pii_sync(pii_engine* e, uint64_t totals[3]) {
             if (e->last_kind == 1 && need_wf > e->wfd_cap) {
                 if ((rc = grow(e, e->wfd, need_wf))) return rc;
                 e->wfd_cap = need_wf;
+            }
+            if (e->excl_ran) {      // k_exclude's occurrence list: its count pass left the exact need (0 if it did not run)
+                uint64_t need_x = 0;
+                HIPCHK(hipMemcpy(&need_x, e->xbase + 2ull * e->last_lanes, sizeof(need_x), hipMemcpyDeviceToHost));
+                if (need_x > e->xocc_cap) {
+                    if ((rc = grow(e, e->xocc, need_x + 4096))) return rc;
+                    e->xocc_cap = need_x + 4096;
+                }
             }
         }
         if ((rc = rerun_last(e))) return rc;
@@ -6536,6 +6794,11 @@ int pii_scratch_bytes(pii_engine* e, uint64_t* used) {
 int pii_window_mode(pii_engine* e) {
     if (!e || e->win_n == 0) return PII_E_ARG;
     return e->win_full ? PII_WINDOW_FULL : 0;
+}
+
+int pii_exclusion_mode(pii_engine* e) {
+    if (!e) return PII_E_ARG;
+    return e->excl_general ? PII_EXCLUSION_GENERAL : PII_EXCLUSION_STREAMING;
 }
 
 int pii_window_reset(pii_engine* e, uint32_t slot) {

@@ -16,6 +16,8 @@ constexpr uint32_t DFA_STATE_MASK = 0x3fffu;
 namespace {
 
 constexpr int NE_MAX = 2;          // excluder patterns
+constexpr int NX_MAX = 64;         // excluder patterns of a GENERAL rule set (k_exclude; compiler.py mirrors both)
+constexpr uint16_t XG_PARTIAL = 0x8000;   // general exclusion list entry: excluder type | this bit for PARTIAL_MATCH
 constexpr int KW_NONE = 0x7fff;
 
 struct RulesDev {

@@ -166,11 +166,11 @@ inline bool pack_image(const ImageParts& parts, uint32_t aux, HostImage& out) {
 // ------------------------------------------------------------------------------- host rules
 // the tables of the packed rules buffer, in the order they are placed (256-byte aligned sections); the
 // SCAN groups' tables follow TB_XF_MASK, the hash tables come after every other table (rules without a
-// hash type keep their layout)
+// hash type keep their layout), the general exclusion tables after those (likewise)
 enum { TB_CMAP4, TB_TD, TB_TK, TB_D_ACCID, TB_D_ACC_OFF, TB_D_ACC_IDS, TB_K_ACCID, TB_K_ACC_MIN, TB_D_NPAIR, TB_K_GRP,
        TB_D_NA, TB_DET_TYPE, TB_DET_VAL, TB_DET_LIK, TB_DET_EXIDX, TB_FIRST_DESC, TB_HOT_RULE, TB_HOT_DESC,
        TB_VAR_ENABLED, TB_VAR_MINLIK, TB_RULE_OFF, TB_RULE_IDS, TB_EXCL_OFF, TB_EXCL_IDS, TB_TOK_OFF, TB_TOK_BYTES,
-       TB_TOK_LEN, TB_XF_KIND, TB_XF_MASK, TB_HASH_KEY, TB_HASH_MID, TB_N };
+       TB_TOK_LEN, TB_XF_KIND, TB_XF_MASK, TB_HASH_KEY, TB_HASH_MID, TB_XG_OFF, TB_XG_IDS, TB_XG_IDX, TB_N };
 enum { GT_CMAP4, GT_TD, GT_TK, GT_D_ACCID, GT_K_ACCID, GT_D_NPAIR, GT_N };
 
 // a SCAN group >= 1: its own D automaton and class map, a 1-row never-accepting K stub
@@ -202,6 +202,10 @@ struct HostRules {
     std::vector<uint8_t> xf_kind;
     bool xf_src = false, xf_mask = false, xf_hash = false;
     bool window_ok = false;
+    // general exclusion rules (var.xg_off / var.xg_ids / det.xgidx): k_exclude decides them, the
+    // streaming lists are empty; excl_nx = its excluder patterns
+    bool excl_general = false;
+    int excl_nx = 0;
 };
 
 // entry (row, class) = address of the destination row | accept | accept of the destination's
@@ -344,6 +348,34 @@ inline const char* build_host_rules(const uint8_t* blob, size_t n, const RuleKno
             if (ex[p] != 0xff) ne = std::max(ne, ex[p] + 1);
         if (ne > NE_MAX) return "too many excluder patterns";
         R.NE = ne;
+    }
+    // general exclusion rules: the three sections together or not at all, beside empty streaming lists
+    const Section *xs_goff = find("var.xg_off"), *xs_gids = find("var.xg_ids"), *xs_gidx = find("det.xgidx");
+    if (xs_goff || xs_gids || xs_gidx) {
+        if (!xs_goff || !xs_gids || !xs_gidx) return "general exclusion sections are not all present";
+        if (R.V < 0 || R.T < 0 || R.P < 0) return "general exclusion tables malformed";
+        const size_t keys = (size_t)R.V * R.T;
+        if (xs_goff->bytes != (keys + 1) * 4) return "var.xg_off does not hold V*T+1 offsets";
+        if (xs_gidx->bytes != (size_t)R.P) return "det.xgidx does not hold one index per pattern";
+        const uint32_t* go = reinterpret_cast<const uint32_t*>(xs_goff->data);
+        const uint16_t* gi = reinterpret_cast<const uint16_t*>(xs_gids->data);
+        if (go[0] != 0) return "var.xg_off does not start at 0";
+        for (size_t k = 0; k < keys; ++k)
+            if (go[k] > go[k + 1]) return "var.xg_off is not ascending";
+        if ((uint64_t)go[keys] * 2 > xs_gids->bytes) return "var.xg_ids is shorter than its offsets";
+        for (uint32_t q = 0; q < go[keys]; ++q)
+            if ((gi[q] & (XG_PARTIAL - 1)) >= R.T) return "var.xg_ids names a type past the type table";
+        int nx = 0;
+        for (int p = 0; p < R.P; ++p)
+            if (xs_gidx->data[p] != 0xff) {
+                if (xs_gidx->data[p] >= NX_MAX) return "det.xgidx holds an index past the limit";
+                nx = std::max(nx, xs_gidx->data[p] + 1);
+            }
+        const Section* xo = find("var.excl_off");
+        if (R.NE != 0 || xo->bytes < (keys + 1) * 4 || reinterpret_cast<const uint32_t*>(xo->data)[keys] != 0)
+            return "general exclusion sections beside streaming exclusion lists";
+        H.excl_general = true;
+        H.excl_nx = nx;
     }
     // deidentify_config: without the sections every type is replaced by its "[NAME]" token
     static const char* xf_bad = "transformation tables malformed";
@@ -500,6 +532,11 @@ inline const char* build_host_rules(const uint8_t* blob, size_t n, const RuleKno
     if (H.xf_hash) {
         H.off[TB_HASH_KEY] = put(xs_hkey->data, xs_hkey->bytes);
         H.off[TB_HASH_MID] = put(xs_hmid->data, xs_hmid->bytes);
+    }
+    if (H.excl_general) {
+        H.off[TB_XG_OFF] = put(xs_goff->data, xs_goff->bytes);
+        H.off[TB_XG_IDS] = put(xs_gids->data, xs_gids->bytes);
+        H.off[TB_XG_IDX] = put(xs_gidx->data, xs_gidx->bytes);
     }
     if (R.n_dacc >= 65535) return "too many SCAN accept sets";
     // per-kernel LDS images

@@ -28,7 +28,7 @@ EXPORTS = ["pii_engine_create", "pii_engine_destroy", "pii_engine_info", "pii_ty
            "pii_window_count", "pii_rescan_window", "pii_rescan_window_device",
            "pii_rescan_window_device_ex", "pii_scan_redact_ext", "pii_scan_redact_device_ext", "pii_window_enable_ex",
            "pii_window_mode", "pii_set_scratch_limit", "pii_scratch_bytes", "pii_context_resize",
-           "pii_context_update", "pii_set_timing", "pii_type_transform"]
+           "pii_context_update", "pii_set_timing", "pii_type_transform", "pii_exclusion_mode"]
 PII_WINDOW_FULL = 1
 # pii_type_transform: what the rules' deidentify_config does with a finding of a type
 PII_XF_INFO_TYPE, PII_XF_REPLACE, PII_XF_REDACT, PII_XF_MASK, PII_XF_KEEP, PII_XF_HASH = range(6)
@@ -107,6 +107,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.pii_window_enable.argtypes = [P, c.c_uint32, c.c_uint32]
     lib.pii_window_enable_ex.argtypes = [P, c.c_uint32, c.c_uint32, c.c_uint32]
     lib.pii_window_mode.argtypes = [P]
+    lib.pii_exclusion_mode.argtypes = [P]
     lib.pii_set_scratch_limit.argtypes = [P, c.c_uint64]
     lib.pii_scratch_bytes.argtypes = [P, U64]
     lib.pii_window_reset.argtypes = [P, c.c_uint32]
@@ -247,6 +248,14 @@ class Engine:
         if rc < 0:
             raise self._err(rc, "pii_window_mode")
         return "full" if rc == PII_WINDOW_FULL else "incremental"
+
+    def exclusion_mode(self) -> int:
+        """0: the rules' exclusions run streaming in k_select; 1: the general pass (k_exclude) decides them
+        (a PARTIAL_MATCH rule, more than two excluder patterns, or a type both excluded and excluding)"""
+        rc = self.lib.pii_exclusion_mode(self.h)
+        if rc < 0:
+            raise self._err(rc, "pii_exclusion_mode")
+        return rc
 
     def window_reset(self, slot: int) -> None:
         rc = self.lib.pii_window_reset(self.h, slot)

@@ -236,6 +236,30 @@ int pii_last_queue_sizes(struct pii_engine* e, uint64_t* pairs, uint64_t* events
  * [8] re-runs the last pii_sync did; fills min(n, 9) entries and returns that count */
 int pii_last_stats(struct pii_engine* e, uint64_t* out, uint32_t n);
 
+/* ---------------------------------------------------------------- exclusion rules (a4)
+ * inspect_config.rule_set[].rules[].exclusion_rule.exclude_info_types, both matching types.  A candidate
+ * c of a rule set's type is dropped when ANOTHER candidate g of a listed type overlaps it
+ * (MATCHING_TYPE_PARTIAL_MATCH: g.start < c.end && c.start < g.end) or contains it
+ * (MATCHING_TYPE_FULL_MATCH: g.start <= c.start && c.end <= g.end) -- oracle/pii_oracle.py find_pii, lines
+ * 383-401 (the min_likelihood filter, then the "a4 exclusion" loop).  Two points of that loop:
+ *   - it runs over the unfiltered candidate list, so an excluder that is itself excluded, or that later
+ *     loses overlap resolution, still excludes (allow-lists chain);
+ *   - g is a candidate: its type is enabled in the row's context variant, its start is not inside its
+ *     own pattern's previous match (re.finditer never reports such a start), and its likelihood after
+ *     validators and hotwords reaches min_likelihood -- tested in that order.
+ * Rules k_select can decide while it streams a lane's candidates (FULL_MATCH only, at most 2 excluder
+ * patterns, no type both excluded and excluding: the shipped rules) run there: PII_EXCLUSION_STREAMING.
+ * Any other rule set (up to 64 excluder patterns) adds a pass between likelihood evaluation and selection
+ * that lists the excluder occurrences of the batch and marks every excluded candidate:
+ * PII_EXCLUSION_GENERAL.  Rows cut into lanes are exact (a cut row's occurrences are gathered by one
+ * thread, serially).  Such rules re-scan windows by the FULL path (pii_window_mode).  Its occurrence list
+ * is a work buffer sized by the batch bytes (pii_reserve covers it); an overflow is re-run by pii_sync like
+ * the other queues.  exclusion_rule.regex / .dictionary / .exclude_by_hotword and rules naming an external
+ * type are refused by the rule compiler. */
+#define PII_EXCLUSION_STREAMING 0
+#define PII_EXCLUSION_GENERAL 1
+int pii_exclusion_mode(struct pii_engine* e);
+
 /* ---------------------------------------------------------------- multi-turn window re-scan (a12)
  * Replaces the aggregator's sliding-window re-scan (README.md:131-134, 159-168: keep the last N
  * utterances of a conversation -- N = 5, transcript_aggregator_service/cloudbuild.yaml:33 -- join
