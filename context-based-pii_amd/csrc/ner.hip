@@ -4,6 +4,7 @@
 //
 // C-ABI (plain device pointers, torch not involved; all calls enqueue on `stream` and return):
 //   ner_gemm       C[M,N] = A[M,K] . W[N,K]^T + bias  (+ exact GELU | + residual)   bf16 in/out, f32 accumulate
+//   ner_gemm_kernel  which kernel ner_gemm launches for [M, N] (host only; the tests' path coverage)
 //   ner_layernorm  y = LN(x) * gamma + beta  per row                                 bf16 in/out, f32 math
 //   ner_embed      LN(word[id] + pos[s] + type[0])                                    -> bf16 hidden
 //   ner_attention  softmax(Q K^T / sqrt(d) + mask) V per (sequence, head) from the fused QKV rows
@@ -798,6 +799,17 @@ __global__ __launch_bounds__(256) void k_ner_spans(const float* __restrict__ log
     ext_n[r] = n;
 }
 
+// The kernel ner_gemm launches for an [M, N] output (M % 128 == 0, N % 128 == 0): the one predicate
+// behind both ner_gemm's dispatch and ner_gemm_kernel's answer.
+enum { GEMM_SINGLE = 0, GEMM_PIPE_128 = 1, GEMM_PIPE_256 = 2 };
+inline int gemm_path(int M, int N) {
+    const long tiles = (long)(M / GB_M) * (N / GB_N);
+    if (!GEMM_PIPE || tiles > 16L * 256) return GEMM_SINGLE;
+    // 256-row tiles when they still give every CU at least two tiles, else 128-row tiles
+    const bool big = GEMM_BIG && M % 256 == 0 && (long)(M / 256) * (N / GB_N) >= 512;
+    return big ? GEMM_PIPE_256 : GEMM_PIPE_128;
+}
+
 }  // namespace
 
 extern "C" {
@@ -821,9 +833,15 @@ int ner_spans(const float* logits, int L, const uint32_t* tok_lo, const uint32_t
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
+// Which kernel ner_gemm launches for a valid [M, N] (host only, nothing is enqueued): 0 = k_gemm,
+// 1 = k_gemm2 with 128-row tiles, 2 = k_gemm2 with 256-row tiles.
+int ner_gemm_kernel(int M, int N) { return gemm_path(M, N); }
+
 int ner_gemm(const void* A, const void* W, const void* bias, const void* resid, void* C, int M, int N, int K,
              int epi, void* stream) {
-    if (!A || !W || !C || M % GB_M || N % GB_N || K % GB_K || M <= 0 || epi < 0 || epi > 2 || (epi == 2 && !resid))
+    // K <= 0 included: the kernels stage K slab 0 before they look at K
+    if (!A || !W || !C || M % GB_M || N % GB_N || K % GB_K || M <= 0 || N <= 0 || K <= 0 || epi < 0 || epi > 2 ||
+        (epi == 2 && !resid))
         return -1;
     const uint16_t *a = static_cast<const uint16_t*>(A), *w = static_cast<const uint16_t*>(W);
     const uint16_t* rs = static_cast<const uint16_t*>(resid);
@@ -834,11 +852,9 @@ int ner_gemm(const void* A, const void* W, const void* bias, const void* resid, 
     // chip's workgroup slots; past that (the NER on the redaction path: M = 524288 tokens) the
     // single-buffer k_gemm's 3-4 workgroups per CU hide the DMA better (QKV 759 vs 647 TFLOP/s there,
     // 597 vs 634 at M = 8192; tools/gemm_ab.py, GEMM_M)
-    const long tiles = (long)(M / GB_M) * (N / GB_N);
-    if (GEMM_PIPE && tiles <= 16L * 256) {
-        // 256-row tiles when they still give every CU at least two tiles, else 128-row tiles
-        const bool big = GEMM_BIG && M % 256 == 0 && (M / 256) * (N / GB_N) >= 512;
-        if (big) {
+    const int path = gemm_path(M, N);
+    if (path != GEMM_SINGLE) {
+        if (path == GEMM_PIPE_256) {
             auto kern = epi == EPI_GELU ? k_gemm2<EPI_GELU, 256, GEMM_MF, GEMM_NB> : epi == EPI_RESID ? k_gemm2<EPI_RESID, 256, GEMM_MF, GEMM_NB>
                                                                                      : k_gemm2<EPI_BIAS, 256, GEMM_MF, GEMM_NB>;
             kern<<<(M / 256) * (N / GB_N), 512, 0, st>>>(a, w, b, rs, c, M, N, K);
@@ -857,7 +873,7 @@ int ner_gemm(const void* A, const void* W, const void* bias, const void* resid, 
 
 int ner_layernorm(const void* x, const float* gamma, const float* beta, void* y, int M, int H, float eps,
                   void* stream) {
-    if (!x || !gamma || !beta || !y || H > 64 * LN_PER || M <= 0) return -1;
+    if (!x || !gamma || !beta || !y || H <= 0 || H > 64 * LN_PER || M <= 0) return -1;
     k_layernorm<<<(M + 3) / 4, 256, 0, static_cast<hipStream_t>(stream)>>>(
         static_cast<const uint16_t*>(x), gamma, beta, static_cast<uint16_t*>(y), M, H, eps);
     return hipGetLastError() == hipSuccess ? 0 : -3;
@@ -865,7 +881,7 @@ int ner_layernorm(const void* x, const float* gamma, const float* beta, void* y,
 
 int ner_embed(const int32_t* ids, const void* wemb, const void* pemb, const void* temb, const float* gamma,
               const float* beta, void* out, int M, int S, int H, float eps, void* stream) {
-    if (!ids || !wemb || !pemb || !temb || !out || H > 64 * LN_PER || M <= 0 || S <= 0) return -1;
+    if (!ids || !wemb || !pemb || !temb || !out || H <= 0 || H > 64 * LN_PER || M <= 0 || S <= 0) return -1;
     k_embed<<<(M + 3) / 4, 256, 0, static_cast<hipStream_t>(stream)>>>(
         ids, static_cast<const uint16_t*>(wemb), static_cast<const uint16_t*>(pemb),
         static_cast<const uint16_t*>(temb), gamma, beta, static_cast<uint16_t*>(out), M, S, H, eps);
@@ -893,7 +909,7 @@ int ner_attention(const void* qkv, const int32_t* mask, void* out, int B, int S,
 }
 
 int ner_classify(const void* h, const void* Wc, const float* bc, float* logits, int M, int H, int L, void* stream) {
-    if (!h || !Wc || !bc || !logits || M <= 0 || L <= 0) return -1;
+    if (!h || !Wc || !bc || !logits || M <= 0 || H <= 0 || L <= 0) return -1;
     k_classify<<<(M + 3) / 4, 256, 0, static_cast<hipStream_t>(stream)>>>(
         static_cast<const uint16_t*>(h), static_cast<const uint16_t*>(Wc), bc, logits, M, H, L);
     return hipGetLastError() == hipSuccess ? 0 : -3;

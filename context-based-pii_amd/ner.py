@@ -54,7 +54,9 @@ def open_library(path: str) -> ctypes.CDLL:
     lib.ner_classify.argtypes = [P, P, P, P, I, I, I, P]
     lib.ner_tokenize.argtypes = [P, P, I, I, I, P, P, P, P, P, P]
     lib.ner_spans.argtypes = [P, I, P, P, P, I, I, I, I, P, P, P]
-    for n in ("ner_gemm", "ner_layernorm", "ner_embed", "ner_attention", "ner_classify", "ner_tokenize", "ner_spans"):
+    lib.ner_gemm_kernel.argtypes = [I, I]      # host only: 0 = k_gemm, 1 / 2 = k_gemm2 with 128- / 256-row tiles
+    for n in ("ner_gemm", "ner_gemm_kernel", "ner_layernorm", "ner_embed", "ner_attention", "ner_classify",
+              "ner_tokenize", "ner_spans"):
         getattr(lib, n).restype = ctypes.c_int
     return lib
 
