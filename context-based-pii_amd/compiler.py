@@ -253,6 +253,21 @@ def add_pattern(nfa: NFA, pattern: str, pid: int, reverse: bool) -> int:
     return Emitter(nfa, reverse).emit(list(tree), flags, m)
 
 
+def add_whole(nfa: NFA, pattern: str, pid: int) -> int:
+    r"""`\A(?:pattern)\Z`, built on the parsed tree (the pattern's global flags stay where they are):
+    run unanchored over a text it accepts iff re.fullmatch(pattern, text) -- existence of a match of the
+    whole text, whatever the alternation order."""
+    tree = parse(pattern)
+    flags = tree.state.flags
+    if flags & C.SRE_FLAG_MULTILINE:
+        raise RuleError("MULTILINE is not supported")
+    if _items_nullable(list(tree)):
+        raise RuleError(f"pattern {pattern!r} can match the empty string")
+    m = nfa.add(MATCH, pid)
+    items = [(C.AT, C.AT_BEGINNING_STRING)] + list(tree) + [(C.AT, C.AT_END_STRING)]
+    return Emitter(nfa, False).emit(items, flags, m)
+
+
 # ================================================================================ byte classes ==
 def byte_classes(nfa: NFA) -> Tuple[np.ndarray, List[int]]:
     """Coarsest partition of 0..255 respecting every CHAR set and the word-character set."""
@@ -1244,6 +1259,60 @@ NX_MAX = 64                     # excluder patterns of a general rule set
 XG_PARTIAL = 0x8000             # var.xg_ids entry: excluder type id | this bit for MATCHING_TYPE_PARTIAL_MATCH
 MATCHING_TYPES = ("MATCHING_TYPE_FULL_MATCH", "MATCHING_TYPE_PARTIAL_MATCH")
 DICT_SCAN_PREFIX = 4            # SCAN prefix of dictionary infoTypes (Rules)
+# Exclusion rules that test the candidate's own text (exclusion_rule.regex / .dictionary, by matching
+# type) or the text around it (exclusion_rule.exclude_by_hotword): k_excl_text runs the rule's HOT-form
+# automaton over the quote or the proximity windows.  xt.rule entry = (kind, window_before, window_after, 0).
+XT_SEARCH, XT_FULL, XT_INVERSE, XT_HOTWORD = range(4)
+XT_FORMS = ("exclude_info_types", "regex", "dictionary", "exclude_by_hotword")
+XT_KIND = {"MATCHING_TYPE_FULL_MATCH": XT_FULL, "MATCHING_TYPE_PARTIAL_MATCH": XT_SEARCH,
+           "MATCHING_TYPE_INVERSE_MATCH": XT_INVERSE}
+
+
+@dataclass(frozen=True)
+class TextExcl:
+    """one text exclusion rule: `pattern` is searched in the quote (XT_SEARCH), must match all of it
+    (XT_FULL: drop, XT_INVERSE: keep), or is searched in the proximity windows (XT_HOTWORD)"""
+    kind: int
+    pattern: str
+    window_before: int = 0
+    window_after: int = 0
+
+
+def parse_text_exclusion(ex: dict) -> TextExcl:
+    """exclusion_rule.regex / .dictionary / .exclude_by_hotword -> TextExcl, or the RuleError naming the
+    field that is not supported"""
+    mt = ex.get("matching_type", "MATCHING_TYPE_FULL_MATCH")
+    if mt not in XT_KIND:
+        raise RuleError(f"exclusion_rule: unknown matching_type {mt}")
+    if "regex" in ex:
+        rx = ex["regex"] or {}
+        if rx.get("group_indexes"):
+            raise RuleError("exclusion_rule.regex.group_indexes is not supported")
+        if not isinstance(rx.get("pattern"), str):
+            raise RuleError("exclusion_rule.regex without a pattern")
+        return TextExcl(XT_KIND[mt], rx["pattern"])
+    if "dictionary" in ex:
+        dc = ex["dictionary"] or {}
+        if "cloud_storage_path" in dc:
+            raise RuleError("exclusion_rule.dictionary.cloud_storage_path is not supported (use word_list)")
+        words = [str(w) for w in ((dc.get("word_list") or {}).get("words") or [])]
+        if not words or any(not w for w in words):
+            raise RuleError("exclusion_rule.dictionary.word_list.words is empty")
+        for w in words:
+            if not w.isascii():
+                raise RuleError(f"exclusion_rule.dictionary.word_list.words: {w!r} is not ASCII")
+        return TextExcl(XT_KIND[mt], r"(?i)\b(?:" + "|".join(re.escape(w) for w in words) + r")\b")
+    hw = ex["exclude_by_hotword"] or {}
+    rx = hw.get("hotword_regex") or {}
+    if rx.get("group_indexes"):
+        raise RuleError("exclusion_rule.exclude_by_hotword.hotword_regex.group_indexes is not supported")
+    if not isinstance(rx.get("pattern"), str):
+        raise RuleError("exclusion_rule.exclude_by_hotword without a hotword_regex.pattern")
+    prox = hw.get("proximity") or {}
+    wb, wa = int(prox.get("window_before", 0) or 0), int(prox.get("window_after", 0) or 0)
+    if wb < 0 or wa < 0 or (wb == 0 and wa == 0):
+        raise RuleError("exclusion_rule.exclude_by_hotword.proximity has no window_before / window_after")
+    return TextExcl(XT_HOTWORD, rx["pattern"], wb, wa)
 
 
 def _table_bytes(m: MealyDFA) -> int:
@@ -1361,7 +1430,11 @@ def plan_scan_groups(rules: Rules, budget: int, k_bytes: int) -> List[Tuple[List
     return out
 
 
-def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
+def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET, text_exclusions: bool = False) -> Compiled:
+    """text_exclusions: compile exclusion_rule.regex / .dictionary / .exclude_by_hotword (parse_text_exclusion).
+    Off, the call keeps the contract it always had -- those forms are a RuleError naming the form -- so a
+    caller that has not asked for them never gets a general rule set it did not expect; compile_default,
+    the entry point of the service and the tools, asks for them."""
     P = len(rules.patterns)
     G = len(rules.kw_groups)
     if P == 0:
@@ -1415,6 +1488,10 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
     rule_ids: List[int] = []
     excl_off = np.zeros(V * T + 1, dtype=np.uint32)
     excl_ids: List[int] = []
+    xt_rules: List[TextExcl] = []
+    xt_index: Dict[TextExcl, int] = {}
+    xt_off = np.zeros(V * T + 1, dtype=np.uint32)
+    xt_ids: List[int] = []
     for v, insp in enumerate(rules.variants()):
         enabled = {it.get("name") for it in insp.get("info_types", [])}
         enabled |= {c.get("info_type", {}).get("name") for c in insp.get("custom_info_types", []) or []}
@@ -1424,6 +1501,7 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
         var_minlik[v] = lik_value(insp.get("min_likelihood", DEFAULT_MIN_LIKELIHOOD))
         per_type_rules = [[] for _ in range(T)]
         per_type_excl = [[] for _ in range(T)]
+        per_type_xt = [[] for _ in range(T)]
         for rs in insp.get("rule_set", []) or []:
             tnames = [it.get("name") for it in rs.get("info_types", [])]
             for rule in rs.get("rules", []):
@@ -1444,10 +1522,22 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
                             per_type_rules[rules.type_id[tn]].append(hot_index[key])
                 elif "exclusion_rule" in rule:
                     ex = rule["exclusion_rule"]
-                    if "exclude_info_types" not in ex:
-                        form = next((k for k in ("regex", "dictionary", "exclude_by_hotword") if k in ex), None)
-                        raise RuleError(f"exclusion_rule.{form} is not supported (only exclude_info_types)" if form
-                                        else "exclusion_rule without exclude_info_types")
+                    forms = [k for k in XT_FORMS if k in ex]
+                    if len(forms) != 1:
+                        raise RuleError("exclusion_rule with " + (" and ".join(forms) if forms else
+                                                                  "none of " + ", ".join(XT_FORMS)))
+                    if forms[0] != "exclude_info_types":
+                        if not text_exclusions:
+                            raise RuleError(f"exclusion_rule.{forms[0]} is not supported by this call "
+                                            "(compile_rules(text_exclusions=True), compile_default)")
+                        tx = parse_text_exclusion(ex)
+                        if tx not in xt_index:
+                            xt_index[tx] = len(xt_rules)
+                            xt_rules.append(tx)
+                        for tn in tnames:
+                            if tn in rules.type_id:
+                                per_type_xt[rules.type_id[tn]].append(xt_index[tx])
+                        continue
                     mt = ex.get("matching_type", "MATCHING_TYPE_FULL_MATCH")
                     if mt not in MATCHING_TYPES:
                         raise RuleError(f"exclusion_rule: unknown matching_type {mt}")
@@ -1459,13 +1549,15 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
                                                                     for x in xs if x in rules.type_id)
         for x in rules.external_types:
             xt = rules.type_id[x]
-            if per_type_rules[xt] or per_type_excl[xt] or any(xt in [i & ~XG_PARTIAL for i in l] for l in per_type_excl):
+            if per_type_rules[xt] or per_type_excl[xt] or per_type_xt[xt] or any(xt in [i & ~XG_PARTIAL for i in l] for l in per_type_excl):
                 raise RuleError(f"external type {x} cannot be named by a hotword or exclusion rule")
         for t in range(T):
             rule_ids.extend(per_type_rules[t])
             rule_off[v * T + t + 1] = len(rule_ids)
             excl_ids.extend(per_type_excl[t])
             excl_off[v * T + t + 1] = len(excl_ids)
+            xt_ids.extend(per_type_xt[t])
+            xt_off[v * T + t + 1] = len(xt_ids)
     # excluder patterns (their type is excluded-against in some variant) get a slot in the resolve
     # kernel's private state and come FIRST in every SCAN-D accept set, so that a same-start
     # excluder is known before the findings it may exclude (A.5).
@@ -1481,7 +1573,9 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
     # k_select keeps, or a type both excluded and excluding.  The lists move to var.xg_* / det.xgidx (read
     # by k_exclude, which marks the excluded candidates before k_select runs) and the streaming tables stay
     # empty.
-    general = (any(i & XG_PARTIAL for i in excl_ids) or ne > NE_MAX or bool(excluder_types & excluded_types))
+    # ... or a rule that tests text (xt_rules): k_excl_text marks its candidates where k_exclude marks.
+    general = (any(i & XG_PARTIAL for i in excl_ids) or ne > NE_MAX or bool(excluder_types & excluded_types)
+               or bool(xt_rules))
     xg_sections = OrderedDict()
     if general:
         if ne > NX_MAX:
@@ -1495,6 +1589,31 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
         excl_ids = []
         exidx = np.full(P, 0xFF, dtype=np.uint8)
         window_ok = 0          # k_win_select's streaming exclusion cannot look ahead: windows re-scan in FULL
+    if xt_rules:
+        # text exclusion rules: per-(variant, type) rule lists, per rule (kind, window_before, window_after, 0)
+        # and a HOT-form automaton in a pool of its own -- FULL / INVERSE: of \A(?:pattern)\Z, accepting
+        # on the quote iff re.fullmatch does; SEARCH / HOTWORD: of the pattern (re.search)
+        if len(xt_rules) > 0xFFFF:
+            raise RuleError(f"{len(xt_rules)} text exclusion rules (more than {0xFFFF})")
+        xt_dfas = []
+        for tx in xt_rules:
+            n4 = NFA()
+            st = (add_whole(n4, tx.pattern, 0) if tx.kind in (XT_FULL, XT_INVERSE)
+                  else add_pattern(n4, tx.pattern, 0, reverse=False))
+            xt_dfas.append(build_set_dfa(n4, [st], unanchored=True))
+        xt_desc, tro, flo = [], 0, 0
+        for i, d in enumerate(xt_dfas):
+            xt_desc.append((tro, flo, 256 * i, d.n_classes + 1, d.start[0], d.start[1], d.start[2], d.n_states))
+            tro += d.trans.size
+            flo += d.flags.size
+        xg_sections["var.xt_off"] = xt_off
+        xg_sections["var.xt_ids"] = np.array(xt_ids, dtype=np.uint16)
+        xg_sections["xt.rule"] = np.array([(tx.kind, tx.window_before, tx.window_after, 0) for tx in xt_rules],
+                                          dtype=np.int32).reshape(-1)
+        xg_sections["xt.desc"] = np.array(xt_desc, dtype=np.int32).reshape(-1)
+        xg_sections["xt.trans"] = np.concatenate([d.trans.reshape(-1) for d in xt_dfas]).astype(np.uint16)
+        xg_sections["xt.flags"] = np.concatenate([d.flags for d in xt_dfas]).astype(np.uint8)
+        xg_sections["xt.cmap"] = np.concatenate([d.cmap for d in xt_dfas]).astype(np.uint8)
     # one accept-set id space over all scan groups: group g's set a > 0 -> acc_base[g] + a
     acc_sets: List[Tuple[int, ...]] = [()]
     acc_base = []
@@ -1590,7 +1709,8 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET) -> Compiled:
             S[f"scan.g{g}.accid"] = global_accid(g, m)
     # deidentify_config: per-type kind, replacement strings, mask parameters (absent: "[TYPE]" for all)
     S.update(transform_sections(rules.transforms))
-    # general exclusion rules: per-(variant, type) lists with the matching bit, per-pattern excluder index
+    # general exclusion rules: per-(variant, type) lists with the matching bit, per-pattern excluder index;
+    # text exclusion rules after them
     S.update(xg_sections)
     blob = _sections_to_blob(S)
     return Compiled(rules, scan_d, scan_k, first, hot, hot_rules, S, blob, [[p.pid for p in ps] for ps, _ in groups])
@@ -1625,7 +1745,7 @@ def compile_default(dlp_config_path: Optional[str] = None, builtin_path: Optiona
                                     default=str).encode()).hexdigest()[:16]
     if key in _CACHE:
         return _CACHE[key]
-    c = compile_rules(rules)
+    c = compile_rules(rules, text_exclusions=True)
     _CACHE[key] = c
     return c
 

@@ -2826,6 +2826,109 @@ __global__ __launch_bounds__(256) void k_excl_mark(const ExclTabs X, const Geo g
     }
 }
 
+// ---------------------------------------------------------------------------- text exclusion
+// k_excl_text: the exclusion rules that test text instead of other candidates (exclusion_rule.regex and
+// .dictionary by matching type, .exclude_by_hotword; compiler.py TextExcl).  Per matched pair that is still
+// a candidate (lik >= 0) and whose (variant, type) has a rule list: the rule's HOT-form automaton over the
+// candidate's own bytes [s, e) -- its edges are text edges, as for re on text[s:e] -- or over the hotword
+// windows clipped to the row; the first rule that drops it stores lik = -1, which k_select reads as
+// k_exclude's mark (the pair still feeds its pattern's finditer state, it no longer competes).  Launched
+// after k_excl_occ<true>: the occurrences were collected from the unmarked candidates, so a candidate
+// dropped here still excludes others through exclude_info_types.  Positions are row relative and a rule
+// reads nothing but the row's bytes, so a row cut into lanes needs no carried state.  The matched pairs
+// are spread over the grid as k_pair_eval spreads them.
+struct TextExclTabs {
+    Pool pool;
+    const int32_t* desc;
+    const int32_t* rule;      // kind, window_before, window_after, 0
+    const uint16_t* dtype;
+    const void* ix;           // rule lists (list_range)
+    uint32_t w;
+    const uint32_t* loff;
+    const uint16_t* ids;
+};
+
+// hot_run with hot_span_pre: a quote or a hotword window is short, so every chunk is loaded before the first step
+__device__ __forceinline__ bool hot_run_pre(const Pool& pool, const int32_t* d, const uint8_t* text, int lo, int hi) {
+    const uint16_t* tr = pool.trans + d[0];
+    const uint8_t* cm = pool.cmap + d[2];
+    const uint32_t nc = (uint32_t)d[3];
+    uint32_t st = (uint32_t)d[4];
+    if (hot_span_pre(tr, cm, nc, text, lo, hi, st)) return true;
+    return (tr[st * nc + nc - 1] & 0x4000u) != 0;
+}
+
+// does a rule of list [r0, r1) drop the candidate [s, e) of row t0[0, L)?
+__device__ __forceinline__ bool text_excluded(const TextExclTabs& X, uint32_t r0, uint32_t r1, const uint8_t* t0, int L,
+                                              int s, int e) {
+    for (uint32_t q = r0; q < r1; ++q) {
+        const uint32_t h = X.ids[q];
+        const int kind = X.rule[4 * h];
+        const int32_t* d = X.desc + 8 * h;
+        const int wb = X.rule[4 * h + 1], wa = X.rule[4 * h + 2];
+        // the quote, or window_before then window_after: one call site (one copy of the runner's registers),
+        // as in pair_lik
+        bool acc = false;
+#pragma unroll 1
+        for (int side = 0; side < (kind == XT_HOTWORD ? 2 : 1) && !acc; ++side) {
+            int lo = s, hi = e;
+            if (kind == XT_HOTWORD) {
+                const int w = side ? wa : wb;
+                lo = side ? e : (s - w > 0 ? s - w : 0);
+                hi = side ? (w < L - e ? e + w : L) : s;          // (no overflow, whatever the window)
+                if (w <= 0) continue;
+            }
+            acc = hot_run_pre(X.pool, d, t0, lo, hi);
+        }
+        const bool drop = acc != (kind == XT_INVERSE);
+        if (drop) return true;
+    }
+    return false;
+}
+
+// (a work unit holds few pairs -- a k_pair_first workgroup's matches over `split` -- and each is a chain of
+// dependent loads before its automaton runs: small workgroups, several resident per CU, hide that better
+// than one of PAIR_BLOCK threads)
+constexpr int XTEXT_BLOCK = 256;
+
+template <bool GI>
+__global__ __launch_bounds__(XTEXT_BLOCK) void k_excl_text(const uint4* __restrict__ img, const LdsImage li, int T,
+                                                         const uint8_t* __restrict__ text0,
+                                                         const uint64_t* __restrict__ offs,
+                                                         const unsigned long long* __restrict__ pair_count,
+                                                         uint64_t pair_cap, const uint32_t* __restrict__ matched,
+                                                         const uint32_t* __restrict__ mcount, uint32_t nseg,
+                                                         const EvLoc* __restrict__ evloc,
+                                                         const int32_t* __restrict__ pend,
+                                                         const PairRes* __restrict__ pres, SelRec* __restrict__ sel,
+                                                         uint32_t split) {
+    extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
+    const uint8_t* lb = load_image<GI>(img, li.total, lds4);
+    TextExclTabs X;
+    X.pool = Pool{reinterpret_cast<const uint16_t*>(lb + li.off[TX_TRANS]), lb + li.off[TX_CMAP]};
+    X.desc = reinterpret_cast<const int32_t*>(lb + li.off[TX_DESC]);
+    X.rule = reinterpret_cast<const int32_t*>(lb + li.off[TX_RULE]);
+    X.dtype = reinterpret_cast<const uint16_t*>(lb + li.off[TX_DTYPE]);
+    X.ix = lb + li.off[TX_OFF];
+    X.w = li.aux & 7u;
+    X.loff = reinterpret_cast<const uint32_t*>(lb + li.off[TX_LOFF]);
+    X.ids = reinterpret_cast<const uint16_t*>(lb + li.off[TX_IDS]);
+    const uint8_t* text = text0 + offs[0];
+    __shared__ uint32_t s_mp[PAIR_WAVES + 1];
+    const uint64_t seg = pair_segment(min((uint64_t)*pair_count, pair_cap), nseg * PAIR_WAVES);
+    for (uint32_t gj = blockIdx.x; gj < nseg * split; gj += gridDim.x) {
+        for_group_matched(s_mp, mcount, matched, seg, pres, evloc, pend, text, gj / split, gj % split, split,
+                          [&](uint32_t i, const PairRes& P, const EvLoc&, const uint8_t* t0, int L, int s, int e)
+                              __attribute__((always_inline)) {
+            const SelRec r = sel[i];
+            if (r.lik < 0) return;
+            uint32_t r0, r1;
+            list_range<true>(X.ix, X.w, X.loff, (r.p >> 16) * (uint32_t)T + X.dtype[P.p], r0, r1);
+            if (r0 != r1 && text_excluded(X, r0, r1, t0, L, s, e)) sel[i].lik = -1;
+        });
+    }
+}
+
 // ---------------------------------------------------------------------------- exclusive scans
 __device__ __forceinline__ uint64_t wave_incl_scan(uint64_t x, int lane) {
     for (int d = 1; d < 64; d <<= 1) {
@@ -4858,6 +4961,9 @@ struct pii_engine {
     XOcc* xocc = nullptr;
     uint64_t xocc_cap = 0;
     bool excl_ran = false;             // the last call launched k_exclude: xbase holds its occurrence count
+    bool excl_lists = false;           // the rules hold an exclude_info_types list (else k_exclude's phases are not launched)
+    bool excl_text = false;            // text exclusion rules: k_excl_text and its image
+    DevImage img_xtext;
     RSpan* rsp = nullptr;
     uint64_t cap_rsp = 0;
     uint32_t* tile_first = nullptr;
@@ -5358,19 +5464,29 @@ struct WinFull {
 // the excluded candidates -- after k_pair_eval wrote the likelihoods, before k_select reads them
 int launch_exclude(pii_engine* e, const Call& c, const CallGeo& cg) {
     const uint32_t n_chunks = cg.n_chunks;
-    const ExclIO io{e->lane_pair, e->lane_np, reinterpret_cast<SelRec*>(e->cont), e->pend, e->pair_cap,
-                    e->xcnt,      e->xbase,   e->xocc,                            e->xocc_cap};
-    const size_t lds = (size_t)e->xt.nx * EXCL_BLOCK * sizeof(uint32_t);
-    const uint32_t nb = (n_chunks + EXCL_BLOCK - 1) / EXCL_BLOCK;
-    HIPCHK(hipMemsetAsync(e->xcnt, 0, 2 * (size_t)n_chunks * sizeof(uint32_t), c.st));
-    k_excl_occ<false><<<nb, EXCL_BLOCK, lds, c.st>>>(e->xt, cg.g, io, e->d_err);
-    int rc = exclusive_scan(e, e->xcnt, 2 * n_chunks, e->xbase, c.st);
-    if (rc) return rc;
-    k_excl_occ<true><<<nb, EXCL_BLOCK, lds, c.st>>>(e->xt, cg.g, io, e->d_err);
-    const uint32_t nm = (uint32_t)std::min<uint64_t>((e->pair_cap + 255) / 256, 8ull * e->n_cu);
-    k_excl_mark<<<nm, 256, 0, c.st>>>(e->xt, cg.g, io, cg.pcount, e->d_err);
-    HIPCHK(hipGetLastError());
-    e->excl_ran = true;
+    if (e->excl_lists) {
+        const ExclIO io{e->lane_pair, e->lane_np, reinterpret_cast<SelRec*>(e->cont), e->pend, e->pair_cap,
+                        e->xcnt,      e->xbase,   e->xocc,                            e->xocc_cap};
+        const size_t lds = (size_t)e->xt.nx * EXCL_BLOCK * sizeof(uint32_t);
+        const uint32_t nb = (n_chunks + EXCL_BLOCK - 1) / EXCL_BLOCK;
+        HIPCHK(hipMemsetAsync(e->xcnt, 0, 2 * (size_t)n_chunks * sizeof(uint32_t), c.st));
+        k_excl_occ<false><<<nb, EXCL_BLOCK, lds, c.st>>>(e->xt, cg.g, io, e->d_err);
+        int rc = exclusive_scan(e, e->xcnt, 2 * n_chunks, e->xbase, c.st);
+        if (rc) return rc;
+        k_excl_occ<true><<<nb, EXCL_BLOCK, lds, c.st>>>(e->xt, cg.g, io, e->d_err);
+        const uint32_t nm = (uint32_t)std::min<uint64_t>((e->pair_cap + 255) / 256, 8ull * e->n_cu);
+        k_excl_mark<<<nm, 256, 0, c.st>>>(e->xt, cg.g, io, cg.pcount, e->d_err);
+        HIPCHK(hipGetLastError());
+        e->excl_ran = true;
+    }
+    // text exclusion rules: after the occurrences were written (a candidate dropped here still excludes)
+    if (e->excl_text) {
+        const DevImage& ix = e->img_xtext;
+        (ix.global ? k_excl_text<true> : k_excl_text<false>)<<<e->n_seg * e->k.eval_split, XTEXT_BLOCK, ix.lds(), c.st>>>(
+            ix.d, ix.li, e->R.T, c.text, c.offs, cg.pcount, e->pair_cap, e->matched, e->mcount, e->n_seg, e->evloc, e->pend,
+            e->pres, reinterpret_cast<SelRec*>(e->cont), e->k.eval_split);
+        HIPCHK(hipGetLastError());
+    }
     return PII_OK;
 }
 
@@ -5831,6 +5947,8 @@ bool upload_rules(pii_engine* e, HostRules& H) {
         e->xt.T = R.T;
         e->xt.nx = H.excl_nx;
     }
+    e->excl_lists = H.excl_lists;
+    e->excl_text = H.excl_text;
     // SCAN groups: sg[0] = R; a group >= 1 has its own D tables and a 1-row K stub
     e->scan_lds = H.scan_lds;
     e->n_sg = 1 + (uint32_t)H.groups.size();
@@ -5867,7 +5985,7 @@ bool upload_rules(pii_engine* e, HostRules& H) {
         {"first", {&H.img_first, &e->img_first}},   {"first_hot", {&H.img_first_hot, &e->img_first_hot}},
         {"eval", {&H.img_eval, &e->img_eval}},      {"eval_rg", {&H.img_eval_rg, &e->img_eval_rg}},
         {"sel", {&H.img_sel, &e->img_sel}},         {"sel_rg", {&H.img_sel_rg, &e->img_sel_rg}},
-        {"wsel", {&H.img_wsel, &e->img_wsel}}};
+        {"wsel", {&H.img_wsel, &e->img_wsel}},      {"xtext", {&H.img_xtext, &e->img_xtext}}};
     for (auto& im : ims) {
         if (!upload_image(*im.second.first, *im.second.second)) return false;
         if (e->k.verbose && im.second.second->d)
@@ -5908,7 +6026,7 @@ bool raise_lds_limits(pii_engine* e) {
         {(const void*)k_select<false, true, true>, &e->img_sel}, {(const void*)k_sel_fix<false, true, true>, &e->img_sel},
         {(const void*)k_pair_eval<false, false, true>, &e->img_eval},
         {(const void*)k_win_eval<false>, &e->img_eval},
-        {(const void*)k_win_select<false>, &e->img_wsel}};
+        {(const void*)k_win_select<false>, &e->img_wsel}, {(const void*)k_excl_text<false>, &e->img_xtext}};
     // k_win_halo<false>: its image plus HALO_LDS of tables (the launch falls back to <true> past the LDS)
     if (!raise((const void*)k_win_halo<false>, IMG_LDS_MAX)) return false;
     for (auto& kb : big)
@@ -6007,7 +6125,7 @@ int pii_engine_destroy(pii_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto& kv : e->scratch_sizes) (void)hipFree(kv.first);
     void* ptrs[] = {e->d_rules, e->img_first.d, e->img_first_hot.d, e->img_eval.d, e->img_eval_rg.d, e->img_sel.d,
-                    e->img_sel_rg.d, e->img_wsel.d, e->mcount, e->d_sg, e->d_sg_lds, e->st_group, e->st_ts, e->stamp,
+                    e->img_sel_rg.d, e->img_wsel.d, e->img_xtext.d, e->mcount, e->d_sg, e->d_sg_lds, e->st_group, e->st_ts, e->stamp,
                     e->d_err, e->d_totals, e->lb_ticket};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -6220,11 +6338,15 @@ int pii_last_queue_sizes(pii_engine* e, uint64_t* pairs, uint64_t* events) {
 
 int pii_last_stats(pii_engine* e, uint64_t* out, uint32_t n) {
     if (!e || (!out && n)) return PII_E_ARG;
-    const uint64_t all[9] = {e->h_totals[3], e->h_totals[4], e->last_lanes, 1ull << e->lane_shift, e->h_totals[5],
-                             e->h_totals[1], e->last_gated ? e->h_totals[6] : 0, e->last_long_launched ? 1u : 0u,
-                             e->last_reruns};
-    for (uint32_t i = 0; i < n && i < 9; ++i) out[i] = all[i];
-    return (int)std::min<uint32_t>(n, 9);
+    // ([9]: read from the device when asked for -- after pii_sync, as the others)
+    uint64_t occ = 0;
+    if (n > 9 && e->excl_ran)
+        HIPCHK(hipMemcpy(&occ, e->xbase + 2ull * e->last_lanes, sizeof(occ), hipMemcpyDeviceToHost));
+    const uint64_t all[10] = {e->h_totals[3], e->h_totals[4], e->last_lanes, 1ull << e->lane_shift, e->h_totals[5],
+                              e->h_totals[1], e->last_gated ? e->h_totals[6] : 0, e->last_long_launched ? 1u : 0u,
+                              e->last_reruns, occ};
+    for (uint32_t i = 0; i < n && i < 10; ++i) out[i] = all[i];
+    return (int)std::min<uint32_t>(n, 10);
 }
 
 int pii_last_timings_ex(pii_engine* e, float* ms, uint32_t n) {

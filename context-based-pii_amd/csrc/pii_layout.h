@@ -19,6 +19,11 @@ constexpr int NE_MAX = 2;          // excluder patterns
 constexpr int NX_MAX = 64;         // excluder patterns of a GENERAL rule set (k_exclude; compiler.py mirrors both)
 constexpr uint16_t XG_PARTIAL = 0x8000;   // general exclusion list entry: excluder type | this bit for PARTIAL_MATCH
 constexpr int KW_NONE = 0x7fff;
+// text exclusion rules (k_excl_text; compiler.py XT_*): xt.rule entry = (kind, window_before, window_after, 0).
+// The rule's HOT-form automaton is run over the candidate's own bytes -- SEARCH: an accept drops it; FULL /
+// INVERSE (the automaton of \A(?:pattern)\Z): an accept / no accept drops it -- or, HOTWORD, over the
+// proximity windows around it, clipped to the row: an accept in either drops it.
+enum { XT_SEARCH = 0, XT_FULL = 1, XT_INVERSE = 2, XT_HOTWORD = 3, XT_KINDS = 4 };
 
 struct RulesDev {
     int P, G, T, V, SD, CD, d_start, SK, CK, k_start, n_hot, min_len;
@@ -94,6 +99,9 @@ enum { EV_TRANS, EV_CMAP, EV_HDESC, EV_HRULE, EV_DTYPE, EV_DVAL, EV_DLIK, EV_ROF
 enum { WS_TRANS, WS_CMAP, WS_HDESC, WS_HRULE, WS_DTYPE, WS_DLIK, WS_VEN, WS_VMIN, WS_DEX, WS_XOFF, WS_XIDS,
        WS_TOKOFF, WS_ROFF, WS_RIDS, WS_RLOFF, WS_XLOFF, WS_N };
 enum { SE_DTYPE, SE_VEN, SE_VMIN, SE_DEX, SE_XOFF, SE_XIDS, SE_TOKOFF, SE_XLOFF, SE_N };
+// k_excl_text: the text exclusion rules' automata, the rules, their per-(variant, type) lists (aux = the
+// lists' index width, list_range), the patterns' types
+enum { TX_TRANS, TX_CMAP, TX_DESC, TX_RULE, TX_DTYPE, TX_OFF, TX_IDS, TX_LOFF, TX_N };
 
 constexpr size_t IMG_LDS_MAX = 160 * 1024;
 // k_pair_first<true>'s LDS copy: most of the LDS, one 1024-thread workgroup per CU (config 5: 40 / 78 /

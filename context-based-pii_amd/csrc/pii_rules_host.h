@@ -166,7 +166,8 @@ inline bool pack_image(const ImageParts& parts, uint32_t aux, HostImage& out) {
 // ------------------------------------------------------------------------------- host rules
 // the tables of the packed rules buffer, in the order they are placed (256-byte aligned sections); the
 // SCAN groups' tables follow TB_XF_MASK, the hash tables come after every other table (rules without a
-// hash type keep their layout), the general exclusion tables after those (likewise)
+// hash type keep their layout), the general exclusion tables after those (likewise); the text exclusion
+// rules live in their kernel's image alone
 enum { TB_CMAP4, TB_TD, TB_TK, TB_D_ACCID, TB_D_ACC_OFF, TB_D_ACC_IDS, TB_K_ACCID, TB_K_ACC_MIN, TB_D_NPAIR, TB_K_GRP,
        TB_D_NA, TB_DET_TYPE, TB_DET_VAL, TB_DET_LIK, TB_DET_EXIDX, TB_FIRST_DESC, TB_HOT_RULE, TB_HOT_DESC,
        TB_VAR_ENABLED, TB_VAR_MINLIK, TB_RULE_OFF, TB_RULE_IDS, TB_EXCL_OFF, TB_EXCL_IDS, TB_TOK_OFF, TB_TOK_BYTES,
@@ -195,6 +196,7 @@ struct HostRules {
     std::vector<HostGroup> groups;
     size_t scan_lds = 0;
     HostImage img_first, img_first_hot, img_eval, img_eval_rg, img_sel, img_sel_rg, img_wsel;
+    HostImage img_xtext;               // k_excl_text's (text exclusion rules only)
     uint32_t first_p_hot = 0;
     bool lists_cl = false;
     std::vector<std::string> names;
@@ -206,6 +208,9 @@ struct HostRules {
     // streaming lists are empty; excl_nx = its excluder patterns
     bool excl_general = false;
     int excl_nx = 0;
+    bool excl_lists = false;           // some (variant, type) has an exclude_info_types list: k_exclude's phases run
+    // text exclusion rules (var.xt_off / var.xt_ids / xt.*): k_excl_text decides them (img_xtext)
+    bool excl_text = false;
 };
 
 // entry (row, class) = address of the destination row | accept | accept of the destination's
@@ -376,6 +381,60 @@ inline const char* build_host_rules(const uint8_t* blob, size_t n, const RuleKno
             return "general exclusion sections beside streaming exclusion lists";
         H.excl_general = true;
         H.excl_nx = nx;
+        H.excl_lists = go[keys] != 0;
+    }
+    // text exclusion rules: the seven sections together or not at all, and only beside the general ones
+    static const char* const xt_names[] = {"var.xt_off", "var.xt_ids", "xt.rule", "xt.desc", "xt.trans", "xt.flags",
+                                           "xt.cmap"};
+    const Section* xts[7];
+    int xt_present = 0;
+    for (int i = 0; i < 7; ++i) xt_present += (xts[i] = find(xt_names[i])) != nullptr;
+    DfaPool xp;
+    ListTab xtl;
+    if (xt_present) {
+        if (xt_present != 7) return "text exclusion sections are not all present";
+        if (!H.excl_general) return "text exclusion sections without the general exclusion sections";
+        const Section *s_off = xts[0], *s_ids = xts[1], *s_rule = xts[2], *s_desc = xts[3], *s_tr = xts[4], *s_fl = xts[5],
+                      *s_cm = xts[6];
+        const size_t keys = (size_t)R.V * R.T;
+        const size_t nr = s_rule->bytes / 16;
+        if (nr == 0 || s_rule->bytes % 16 != 0 || nr > 65535) return "xt.rule does not hold whole rules";
+        if (s_desc->bytes != nr * 32) return "xt.desc does not hold one descriptor per rule";
+        if (s_cm->bytes != nr * 256) return "xt.cmap does not hold one class map per rule";
+        if (s_off->bytes != (keys + 1) * 4) return "var.xt_off does not hold V*T+1 offsets";
+        const uint32_t* xo = reinterpret_cast<const uint32_t*>(s_off->data);
+        const uint16_t* xi = reinterpret_cast<const uint16_t*>(s_ids->data);
+        if (xo[0] != 0) return "var.xt_off does not start at 0";
+        for (size_t k = 0; k < keys; ++k)
+            if (xo[k] > xo[k + 1]) return "var.xt_off is not ascending";
+        if ((uint64_t)xo[keys] * 2 > s_ids->bytes) return "var.xt_ids is shorter than its offsets";
+        for (uint32_t q = 0; q < xo[keys]; ++q)
+            if (xi[q] >= nr) return "var.xt_ids names a rule past the rule table";
+        const int32_t* xr = reinterpret_cast<const int32_t*>(s_rule->data);
+        const int32_t* xd = reinterpret_cast<const int32_t*>(s_desc->data);
+        const uint16_t* xtr = reinterpret_cast<const uint16_t*>(s_tr->data);
+        for (size_t r = 0; r < nr; ++r) {
+            const int32_t kind = xr[4 * r], wb = xr[4 * r + 1], wa = xr[4 * r + 2];
+            if (kind < 0 || kind >= XT_KINDS) return "xt.rule holds an unknown kind";
+            if (wb < 0 || wa < 0) return "xt.rule holds a negative window";
+            if (kind == XT_HOTWORD && wb == 0 && wa == 0) return "xt.rule holds a hotword rule without a window";
+            const int32_t* d = xd + 8 * r;
+            const int64_t nc = d[3], ns = d[7];
+            if (nc < 2 || nc > 256 || ns < 1 || ns > (int64_t)pii::DFA_STATE_MASK + 1)
+                return "xt.desc holds an automaton of impossible size";
+            if (d[0] < 0 || (uint64_t)d[0] + (uint64_t)(ns * nc) > s_tr->bytes / 2)
+                return "xt.desc points past xt.trans";
+            if (d[1] < 0 || (uint64_t)d[1] + (uint64_t)ns > s_fl->bytes) return "xt.desc points past xt.flags";
+            if (d[2] < 0 || (uint64_t)d[2] + 256 > s_cm->bytes) return "xt.desc points past xt.cmap";
+            if (d[4] < 0 || d[4] >= ns) return "xt.desc holds a start state past its automaton";
+            for (int64_t i = 0; i < ns * nc; ++i)
+                if (xtr[d[0] + i] >= ns) return "xt.trans holds a state past its automaton";
+            for (int c = 0; c < 256; ++c)
+                if (s_cm->data[d[2] + c] >= nc - 1) return "xt.cmap holds a class past its automaton";
+            if (!add_dfa(xp, d, xtr, s_fl->data, s_cm->data)) return "xt.desc holds an automaton of impossible size";
+        }
+        xtl = dedup_lists(xo, xi, keys);
+        H.excl_text = true;
     }
     // deidentify_config: without the sections every type is replaced by its "[NAME]" token
     static const char* xf_bad = "transformation tables malformed";
@@ -600,6 +659,18 @@ inline const char* build_host_rules(const uint8_t* blob, size_t n, const RuleKno
     if (!pack_image(pw, aux, H.img_wsel) || !pack_image(pf, 0, H.img_first) || !pack_image(pe, aux, H.img_eval) ||
         !pack_image(ps, aux, H.img_sel))
         return img_bad;
+    if (H.excl_text) {
+        ImageParts px(TX_N);
+        px[TX_TRANS] = part(xp.trans);
+        px[TX_CMAP] = part(xp.cmap);
+        px[TX_DESC] = part(xp.desc);
+        px[TX_RULE] = sec("xt.rule");
+        px[TX_DTYPE] = sec("det.type");
+        px[TX_OFF] = part(xtl.ix);
+        px[TX_IDS] = part(xtl.ids);
+        px[TX_LOFF] = part(xtl.loff);
+        if (!pack_image(px, xtl.w, H.img_xtext)) return img_bad;
+    }
     if (H.img_first.global) {
         DfaPool hf;
         const uint32_t ph = pack_first_hot(knobs, R.P, fdesc, ptrans, pflags, pcmap, fpre, hf);

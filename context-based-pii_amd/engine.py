@@ -250,12 +250,22 @@ class Engine:
         return "full" if rc == PII_WINDOW_FULL else "incremental"
 
     def exclusion_mode(self) -> int:
-        """0: the rules' exclusions run streaming in k_select; 1: the general pass (k_exclude) decides them
-        (a PARTIAL_MATCH rule, more than two excluder patterns, or a type both excluded and excluding)"""
+        """0: the rules' exclusions run streaming in k_select; 1: the general pass (k_exclude, k_excl_text)
+        decides them (a PARTIAL_MATCH rule, more than two excluder patterns, a type both excluded and
+        excluding, or any regex / dictionary / exclude_by_hotword exclusion rule)"""
         rc = self.lib.pii_exclusion_mode(self.h)
         if rc < 0:
             raise self._err(rc, "pii_exclusion_mode")
         return rc
+
+    def exclusion_occurrences(self) -> int:
+        """excluder occurrences the last call's general exclusion pass listed (pii_last_stats [9]); 0 when its
+        occurrence phases did not run (streaming rules, or rules without an exclude_info_types list)"""
+        a = (ctypes.c_uint64 * 10)()
+        n = self.lib.pii_last_stats(self.h, a, 10)
+        if n < 10:
+            raise self._err(min(n, -1), "pii_last_stats")
+        return int(a[9])
 
     def window_reset(self, slot: int) -> None:
         rc = self.lib.pii_window_reset(self.h, slot)

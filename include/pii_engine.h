@@ -233,13 +233,17 @@ int pii_last_queue_sizes(struct pii_engine* e, uint64_t* pairs, uint64_t* events
 /* the last call's work sizes: [0] candidate pairs [1] scan events [2] scan lanes [3] bytes per scan lane
  * (1 KiB for big batches, down to 128 B for small ones) [4] window-findings arena entries [5] spans
  * [6] rows cut into several lanes (scan-and-redact calls) [7] 1 if the long-row kernels were launched
- * [8] re-runs the last pii_sync did; fills min(n, 9) entries and returns that count */
+ * [8] re-runs the last pii_sync did [9] excluder occurrences the general exclusion pass listed (0 when its
+ * occurrence phases did not run: streaming rules, or rules without an exclude_info_types list); fills
+ * min(n, 10) entries and returns that count */
 int pii_last_stats(struct pii_engine* e, uint64_t* out, uint32_t n);
 
 /* ---------------------------------------------------------------- exclusion rules (a4)
- * inspect_config.rule_set[].rules[].exclusion_rule.exclude_info_types, both matching types.  A candidate
- * c of a rule set's type is dropped when ANOTHER candidate g of a listed type overlaps it
- * (MATCHING_TYPE_PARTIAL_MATCH: g.start < c.end && c.start < g.end) or contains it
+ * inspect_config.rule_set[].rules[].exclusion_rule, all four forms.  A rule applies to a candidate c of a
+ * type its rule set lists, in the row's context variant.
+ *
+ * exclude_info_types, FULL_MATCH and PARTIAL_MATCH: c is dropped when ANOTHER candidate g of a listed type
+ * overlaps it (MATCHING_TYPE_PARTIAL_MATCH: g.start < c.end && c.start < g.end) or contains it
  * (MATCHING_TYPE_FULL_MATCH: g.start <= c.start && c.end <= g.end) -- oracle/pii_oracle.py find_pii, lines
  * 383-401 (the min_likelihood filter, then the "a4 exclusion" loop).  Two points of that loop:
  *   - it runs over the unfiltered candidate list, so an excluder that is itself excluded, or that later
@@ -247,15 +251,31 @@ int pii_last_stats(struct pii_engine* e, uint64_t* out, uint32_t n);
  *   - g is a candidate: its type is enabled in the row's context variant, its start is not inside its
  *     own pattern's previous match (re.finditer never reports such a start), and its likelihood after
  *     validators and hotwords reaches min_likelihood -- tested in that order.
- * Rules k_select can decide while it streams a lane's candidates (FULL_MATCH only, at most 2 excluder
- * patterns, no type both excluded and excluding: the shipped rules) run there: PII_EXCLUSION_STREAMING.
- * Any other rule set (up to 64 excluder patterns) adds a pass between likelihood evaluation and selection
- * that lists the excluder occurrences of the batch and marks every excluded candidate:
- * PII_EXCLUSION_GENERAL.  Rows cut into lanes are exact (a cut row's occurrences are gathered by one
- * thread, serially).  Such rules re-scan windows by the FULL path (pii_window_mode).  Its occurrence list
- * is a work buffer sized by the batch bytes (pii_reserve covers it); an overflow is re-run by pii_sync like
- * the other queues.  exclusion_rule.regex / .dictionary / .exclude_by_hotword and rules naming an external
- * type are refused by the rule compiler. */
+ *
+ * regex and dictionary (word_list; the pattern (?i)\b(?:w1|w2|...)\b) test the candidate's own bytes,
+ * quote = row[c.start, c.end), whose edges are text edges for \b, \A and \Z: MATCHING_TYPE_FULL_MATCH
+ * (the default) drops c if the pattern matches the whole quote (re.fullmatch), PARTIAL_MATCH if it matches
+ * anywhere in it (re.search), INVERSE_MATCH if it does NOT match the whole quote.  exclude_by_hotword
+ * drops c if hotword_regex matches inside row[c.start - window_before, c.start) or row[c.end, c.end +
+ * window_after), the windows clipped to the row and their edges text edges (the proximity test of a
+ * hotword_rule).  A candidate these rules drop is still a candidate in the loop above: it excludes others
+ * through exclude_info_types and its pattern's next match starts after it; it only leaves before overlap
+ * resolution, so a shorter overlapping candidate of another type can become a finding.  tests/
+ * text_excl_ref.py states this in Python.
+ *
+ * Rules k_select can decide while it streams a lane's candidates (exclude_info_types with FULL_MATCH only,
+ * at most 2 excluder patterns, no type both excluded and excluding: the shipped rules) run there:
+ * PII_EXCLUSION_STREAMING.  Any other rule set (up to 64 excluder patterns; any regex, dictionary or
+ * exclude_by_hotword rule) adds a pass between likelihood evaluation and selection, PII_EXCLUSION_GENERAL:
+ * it lists the excluder occurrences of the batch and marks every candidate they exclude (only when the
+ * rules hold an exclude_info_types list), then runs the text rules' automata over each remaining
+ * candidate of a type that has one and marks those they drop.  Rows cut into lanes are exact (a cut row's
+ * occurrences are gathered by one thread, serially; the text rules read row positions).  Such rules
+ * re-scan windows by the FULL path (pii_window_mode): over the joined window a hotword window reaches
+ * across the "\n" joins.  The occurrence list is a work buffer sized by the batch bytes (pii_reserve covers
+ * it); an overflow is re-run by pii_sync like the other queues.  Refused by the rule compiler:
+ * exclude_info_types with INVERSE_MATCH, regex / hotword_regex group_indexes, dictionary
+ * cloud_storage_path, patterns that match the empty string, and rules naming an external type. */
 #define PII_EXCLUSION_STREAMING 0
 #define PII_EXCLUSION_GENERAL 1
 int pii_exclusion_mode(struct pii_engine* e);
