@@ -3,36 +3,21 @@ stand-alone program of test_rules_host (tests/rules_host_main.cpp, built with th
 address and undefined-behaviour sanitizers) accepts the G1 and G2 blobs and rejects, each with its own
 message, blobs whose general exclusion sections are damaged one at a time."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import yaml
 
 import excl_configs as XC
-from conftest import ROOT, pkg
+import rules_host_runner
+from conftest import pkg
 
-SRC = os.path.join(ROOT, "tests", "rules_host_main.cpp")
 SECTIONS = ("var.xg_off", "var.xg_ids", "det.xgidx")
 
 
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler found (g++, c++ or clang++)"
-    exe = str(tmp_path_factory.mktemp("excl_host") / "rules_host_main")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-o", exe, SRC], check=True)
-    d = tmp_path_factory.mktemp("excl_blobs")
-
-    def go(name: str, blob: bytes) -> str:
-        path = d / (name + ".bin")
-        path.write_bytes(blob)
-        r = subprocess.run([exe, str(path)], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-4000:]
-        return r.stdout.strip()
-    return go
+    return rules_host_runner.runner(tmp_path_factory, "excl_blobs")
 
 
 @pytest.fixture(scope="module")

@@ -3,38 +3,17 @@ program built with the host compiler under the address and undefined-behaviour s
 the blobs the shipped compiler produces and over blobs damaged one section at a time.  The program exits
 0 whether it accepts or rejects a blob; a sanitizer report is the only failure."""
 import os
-import shutil
-import subprocess
 
 import pytest
 
 import blob_damage
-from conftest import ROOT, pkg
-
-SRC = os.path.join(ROOT, "tests", "rules_host_main.cpp")
-
-
-@pytest.fixture(scope="module")
-def prog(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler found (g++, c++ or clang++)"
-    exe = str(tmp_path_factory.mktemp("rules_host") / "rules_host_main")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-o", exe, SRC], check=True)
-    return exe
+import rules_host_runner
+from conftest import pkg
 
 
 @pytest.fixture(scope="module")
-def run(prog, tmp_path_factory):
-    d = tmp_path_factory.mktemp("blobs")
-
-    def go(name: str, blob: bytes) -> str:
-        path = d / (name + ".bin")
-        path.write_bytes(blob)
-        r = subprocess.run([prog, str(path)], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-4000:]
-        return r.stdout.strip()
-    return go
+def run(tmp_path_factory):
+    return rules_host_runner.runner(tmp_path_factory, "blobs")
 
 
 @pytest.fixture(scope="module")
