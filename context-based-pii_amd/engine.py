@@ -28,7 +28,8 @@ EXPORTS = ["pii_engine_create", "pii_engine_destroy", "pii_engine_info", "pii_ty
            "pii_window_count", "pii_rescan_window", "pii_rescan_window_device",
            "pii_rescan_window_device_ex", "pii_scan_redact_ext", "pii_scan_redact_device_ext", "pii_window_enable_ex",
            "pii_window_mode", "pii_set_scratch_limit", "pii_scratch_bytes", "pii_context_resize",
-           "pii_context_update", "pii_set_timing", "pii_type_transform", "pii_exclusion_mode"]
+           "pii_context_update", "pii_set_timing", "pii_type_transform", "pii_exclusion_mode",
+           "pii_rescan_window_ext", "pii_rescan_window_device_ext"]
 PII_WINDOW_FULL = 1
 # pii_type_transform: what the rules' deidentify_config does with a finding of a type
 PII_XF_INFO_TYPE, PII_XF_REPLACE, PII_XF_REDACT, PII_XF_MASK, PII_XF_KEEP, PII_XF_HASH = range(6)
@@ -115,6 +116,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.pii_rescan_window.argtypes = lib.pii_scan_redact.argtypes
     lib.pii_rescan_window_device.argtypes = lib.pii_scan_redact_device.argtypes
     lib.pii_rescan_window_device_ex.argtypes = lib.pii_scan_redact_device_ex.argtypes
+    lib.pii_rescan_window_ext.argtypes = lib.pii_scan_redact_ext.argtypes
+    lib.pii_rescan_window_device_ext.argtypes = lib.pii_scan_redact_device_ext.argtypes
     for name in EXPORTS:
         if name != "pii_last_error":
             getattr(lib, name).restype = c.c_int
@@ -229,11 +232,19 @@ class Engine:
         return self._host_call(fn, "pii_scan_redact_ext", texts, conv_slot, role, ts_us, 1)
 
     def rescan_window(self, texts: Sequence[bytes], conv_slot: Sequence[int], role: Sequence[int],
-                      ts_us: Optional[Sequence[int]] = None) -> BatchResult:
+                      ts_us: Optional[Sequence[int]] = None, ext: Optional[Sequence[Sequence[tuple]]] = None
+                      ) -> BatchResult:
         """Window re-scan (a12): row i's result = its conversation's redacted "\\n".join(last N
-        utterances ending at row i); spans are window offsets; ctx_info = the window's context group."""
+        utterances ending at row i); spans are window offsets; ctx_info = the window's context group.
+        ext[i]: row i's external-detector candidates, as in scan_redact (pii_rescan_window_ext): given once,
+        with the row, they stay with it in every later window that holds it."""
         n = max(1, self.window_n)
-        return self._host_call(self.lib.pii_rescan_window, "pii_rescan_window", texts, conv_slot, role, ts_us, n)
+        if ext is None:
+            return self._host_call(self.lib.pii_rescan_window, "pii_rescan_window", texts, conv_slot, role, ts_us, n)
+        spans, counts, stride = ext_arrays(ext, len(texts))
+        fn = lambda *a: self.lib.pii_rescan_window_ext(*a, _ptr(spans), _ptr(counts), stride)   # noqa: E731
+        # (a window can hold more 1-byte findings than its bytes / 3: _host_call retries with the exact sizes)
+        return self._host_call(fn, "pii_rescan_window_ext", texts, conv_slot, role, ts_us, n)
 
     def window_enable(self, window_n: int = 5, slot_bytes: int = 8192, full: bool = False) -> None:
         """full=True forces the full re-scan of the joined windows (rule sets the incremental path
@@ -295,6 +306,17 @@ class Engine:
                                                   d_ctx, stream)
         if rc != PII_OK:
             raise self._err(rc, "pii_rescan_window_device_ex")
+
+    def rescan_window_device_ext(self, d_bytes, d_offsets, n_utt, batch_base, batch_bytes, d_slot, d_role, d_ts,
+                                 d_out, out_cap, d_out_offsets, d_spans, span_cap, d_ctx, d_ext, d_ext_n, ext_stride,
+                                 stream=None) -> None:
+        """rescan_window_device_ex plus the rows' external candidates in device memory
+        (pii_rescan_window_device_ext): d_ext[row * ext_stride + k] for k < d_ext_n[row]."""
+        rc = self.lib.pii_rescan_window_device_ext(self.h, d_bytes, d_offsets, n_utt, batch_base, batch_bytes, d_slot,
+                                                   d_role, d_ts, d_out, out_cap, d_out_offsets, d_spans, span_cap,
+                                                   d_ctx, d_ext, d_ext_n, ext_stride, stream)
+        if rc != PII_OK:
+            raise self._err(rc, "pii_rescan_window_device_ext")
 
     def _host_call(self, fn, name, texts, conv_slot, role, ts_us, mult) -> BatchResult:
         data, offs = pack(texts)

@@ -333,6 +333,15 @@ class PiiService:
         ext = self.ner.ext_candidates(texts, self.ner_type, max_len=self.ner_max_len)
         return self.engine.scan_redact(texts, slots, roles, ts, ext=ext)
 
+    def _rescan(self, texts: Sequence[bytes], slots: Sequence[int], roles: Sequence[int], ts: Sequence[int]):
+        """engine.rescan_window with the detector's candidates for the NEW rows (pii_rescan_window_ext): a
+        row's names enter its conversation's window with the row and are redacted in every window that
+        holds it; the detector is not run over the joined windows.  No detector: the plain call."""
+        if self.ner is None:
+            return self.engine.rescan_window(texts, slots, roles, ts)
+        ext = self.ner.ext_candidates(texts, self.ner_type, max_len=self.ner_max_len)
+        return self.engine.rescan_window(texts, slots, roles, ts, ext=ext)
+
     def _sub_batches(self, keys: Sequence[object], split_before: Optional[Sequence[bool]] = None) -> List[List[int]]:
         """Row indices cut into runs at the marked rows (the slot table grows instead of evicting a
         live conversation, so a run may hold any number of conversations)."""
@@ -619,12 +628,11 @@ class PiiService:
                 now = self._now_us()
                 slots, code = self.slots.assign([r["conversation_id"] for r in part], pinned, now)
                 if code:
-                    out.extend(self._without_slots(part, slots, code, texts, ts, self.engine.rescan_window,
-                                                   window=True))
+                    out.extend(self._without_slots(part, slots, code, texts, ts, self._rescan, window=True))
                     continue
                 roles = [role_code(r.get("participant_role")) for r in part]
                 try:
-                    res = self.engine.rescan_window(texts, slots, roles, ts)
+                    res = self._rescan(texts, slots, roles, ts)
                 except PiiError as e:
                     # the context is stored regardless (main.py:358-374); the rows do not enter the windows
                     self._note(slots, roles, [r["text"] for r in part], ts,

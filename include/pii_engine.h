@@ -299,7 +299,8 @@ int pii_exclusion_mode(struct pii_engine* e);
 #define PII_WINDOW_MAX 8
 #define PII_WINDOW_FULL 1   /* pii_window_enable_ex flag / pii_window_mode result: full re-scan */
 /* allocate the per-slot window history (n_conv_slots * slot_bytes of HBM); window_n <= PII_WINDOW_MAX,
- * slot_bytes a multiple of 16 (a window must fit: its utterances + 16 B per resident candidate) */
+ * slot_bytes a multiple of 16 (a window must fit: its utterances, each rounded up to 16 B, + 16 B per
+ * resident candidate, external ones (pii_rescan_window_ext) included) */
 int pii_window_enable(struct pii_engine* e, uint32_t window_n, uint32_t slot_bytes);
 /* the same; flags PII_WINDOW_FULL forces the full re-scan even for rules the incremental path takes */
 int pii_window_enable_ex(struct pii_engine* e, uint32_t window_n, uint32_t slot_bytes, uint32_t flags);
@@ -333,6 +334,38 @@ int pii_rescan_window_device_ex(struct pii_engine* e, const uint8_t* d_bytes, co
                                 const uint32_t* d_conv_slot, const uint8_t* d_role, const int64_t* d_ts_us,
                                 uint8_t* d_out_bytes, uint64_t out_cap, uint64_t* d_out_offsets,
                                 pii_span* d_spans, uint32_t span_cap, int16_t* d_win_ctx, void* stream);
+/* pii_rescan_window / pii_rescan_window_device_ex with another detector's candidates for the call's rows
+ * (the NER's PERSON_NAME spans): ext[row * ext_stride + k] for k < ext_n[row], row-relative, under exactly
+ * the contract of pii_scan_redact_ext (start < end <= row length, sorted by start, info_type < n_types,
+ * likelihood 1..5, ext_n <= ext_stride; null pointers or stride 0: PII_E_ARG).  A row's candidates are
+ * given ONCE, with the row, and stay with it for as long as it is in its conversation's window: they are
+ * kept in the history ring as resident candidates (16 B each, like a rule candidate: count them in
+ * slot_bytes), and every window that holds the row redacts
+ *     "\n".join(window) with the candidates of all its entries, each shifted by its entry's offset in the
+ *     joined text (sum of len + 1 over the entries before it)
+ * as oracle find_pii(extra=...) does: the candidates go through the window's context variant (enabled
+ * types, min_likelihood) and overlap resolution; no finditer skipping, no hotword rule, no exclusion on
+ * either side.  A candidate never crosses a "\n".  The detector is NOT run over the joined text: a
+ * window's names are the names each utterance had when it arrived (tests/window_ext_ref.py states this in
+ * Python).  A malformed list fails the call with PII_E_ARG and commits nothing (ring, context record,
+ * histogram).  The plain pii_rescan_window* calls keep their behaviour; on an engine whose rings hold
+ * external candidates they still honour those (their own rows have none).  Incremental mode merges the
+ * candidates into the rows' resident lists (two small kernels and a scan, launched only for a call that
+ * carries candidates; the device form still enqueues without a device-to-host read); the FULL re-scan keeps
+ * them in its otherwise text-only ring entries and hands every joined window's list to the second pass,
+ * its stride (the largest window list, n_utt x stride x 16 B of work buffer) read in the call's one host
+ * wait.  The merged lists are work buffers (pii_set_scratch_limit counts them). */
+int pii_rescan_window_ext(struct pii_engine* e, const uint8_t* bytes, const uint64_t* offsets, uint32_t n_utt,
+                          const uint32_t* conv_slot, const uint8_t* role, const int64_t* ts_us,
+                          uint8_t* out_bytes, uint64_t out_cap, uint64_t* out_offsets,
+                          pii_span* spans, uint32_t span_cap, uint32_t* n_spans, int16_t* win_ctx,
+                          const pii_span* ext, const uint32_t* ext_n, uint32_t ext_stride);
+int pii_rescan_window_device_ext(struct pii_engine* e, const uint8_t* d_bytes, const uint64_t* d_offsets,
+                                 uint32_t n_utt, uint64_t batch_base, uint64_t batch_bytes,
+                                 const uint32_t* d_conv_slot, const uint8_t* d_role, const int64_t* d_ts_us,
+                                 uint8_t* d_out_bytes, uint64_t out_cap, uint64_t* d_out_offsets,
+                                 pii_span* d_spans, uint32_t span_cap, int16_t* d_win_ctx,
+                                 const pii_span* d_ext, const uint32_t* d_ext_n, uint32_t ext_stride, void* stream);
 
 #ifdef __cplusplus
 }
