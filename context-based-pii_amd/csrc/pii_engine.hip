@@ -3687,12 +3687,27 @@ __global__ __launch_bounds__(REDACT_BLOCK) void k_redact(const RulesDev R, const
     }
 }
 
+// The code-point state machine of character_mask_config (k_mask, k_win_mask), one byte per step: b = the byte at
+// o[i], newcp = it starts a code point.  False: number_to_mask code points are masked, the walk ends.
+__device__ __forceinline__ bool mask_step(const uint4& m0, const uint2& m1, uint8_t mc, uint32_t limit,
+                                          uint32_t& masked, bool& cur, uint8_t* o, uint32_t b, int i, bool newcp) {
+    if (newcp) {
+        if (masked >= limit) return false;
+        const uint32_t sw = b < 32u ? m0.z : b < 64u ? m0.w : b < 96u ? m1.x : m1.y;
+        cur = !(b < 128u && ((sw >> (b & 31u)) & 1u));
+        masked += cur ? 1u : 0u;
+    }
+    if (cur) o[i] = mc;
+    return true;
+}
+
 // character_mask_config, after k_redact<true> has copied a mask type's finding to the output unchanged:
 // one thread per span walks the finding's UTF-8 code points (from the end when reverse_order) and
 // overwrites every byte of a masked code point with the masking character, until number_to_mask code
 // points are masked (0 = all).  A single-byte code point in the type's skip set is kept and not
 // counted.  The output length never depends on the text (out_len), so only bytes inside the span's
 // own output range [rs_out, rs_out + in_len) are written.  Launched only for rules with a mask type.
+// (win_mask_walk states the two loops below a second time for k_win_mask: a change here belongs there too)
 __global__ __launch_bounds__(256) void k_mask(const RulesDev R, const uint8_t* __restrict__ text,
                                               const uint64_t* __restrict__ offs, const RSpan* __restrict__ rsp,
                                               const uint64_t* __restrict__ n_spans_p,
@@ -3719,14 +3734,7 @@ __global__ __launch_bounds__(256) void k_mask(const RulesDev R, const uint8_t* _
     uint32_t masked = 0;
     bool cur = false;                            // the code point being walked is masked
     auto step = [&](uint32_t b, int i, bool newcp) -> bool {
-        if (newcp) {
-            if (masked >= limit) return false;
-            const uint32_t sw = b < 32u ? m0.z : b < 64u ? m0.w : b < 96u ? m1.x : m1.y;
-            cur = !(b < 128u && ((sw >> (b & 31u)) & 1u));
-            masked += cur ? 1u : 0u;
-        }
-        if (cur) o[i] = mc;
-        return true;
+        return mask_step(m0, m1, mc, limit, masked, cur, o, b, i, newcp);
     };
     if (!rev) {
         for (int j = 0; j < len; j += 16) {
@@ -3834,6 +3842,8 @@ __device__ __forceinline__ void b64_store(const uint32_t (&d)[9], uint8_t* o) {
 // output length never depends on the text (out_len), so exactly the span's own 44 output bytes are
 // written.  Launched only for rules with a hash type; its two tables (hash_key: per type a key index,
 // hash_mid: per key XF_HASH_KEY_WORDS words) are its own arguments, RulesDev does not carry them.
+// (k_win_hash states the padding and the inner / outer framing below a second time: a change here belongs
+// there too)
 constexpr int HASH_BLOCK = 256;
 __global__ __launch_bounds__(HASH_BLOCK) void k_hash(const uint8_t* __restrict__ xf_kind,
                                                      const uint32_t* __restrict__ hash_key,
@@ -4575,6 +4585,8 @@ __global__ __launch_bounds__(256) void k_win_alloc(const WinRing W, const WinBat
 }
 
 // window output byte `rel` (slow path for windows whose pieces overflow the tile's LDS table)
+// SRC: as in k_win_redact
+template <bool SRC>
 __device__ uint8_t win_byte_slow(const RulesDev& R, const WinRing& W, const WinBatch& B, const WinIt& it,
                                  const pii_span* F, uint32_t nf, uint32_t rel) {
     uint32_t pout = 0, fi = 0, oj = 0;
@@ -4588,7 +4600,9 @@ __device__ uint8_t win_byte_slow(const RulesDev& R, const WinRing& W, const WinB
             pout += run;
             const uint32_t t0 = R.tok_off[F[fi].info_type];
             const uint32_t tl = out_len(R.tok_len, F[fi].info_type, F[fi].end - F[fi].start);
-            if (rel < pout + tl) return R.tok_bytes[t0 + (rel - pout)];
+            if (rel < pout + tl)
+                return SRC && (R.tok_len[F[fi].info_type] & XF_SAME_LEN) ? Ej.t[F[fi].start - oj + (rel - pout)]
+                                                                         : R.tok_bytes[t0 + (rel - pout)];
             pout += tl;
             pin = F[fi].end;
             ++fi;
@@ -4608,7 +4622,10 @@ __device__ uint8_t win_byte_slow(const RulesDev& R, const WinRing& W, const WinB
 // (2 per finding + 2 per entry) overflow the table falls back to one byte per lane and step; with a name
 // on every row 64 windows do (64 x (2 x 5 + 9) = 1216 > PIECE_MAX), so an engine whose rings hold external
 // records tiles by WIN_TILE_XR
-template <int WT = WIN_TILE>
+// SRC: the rules hold a mask / keep type on an engine enabled with PII_WINDOW_XF: such a finding's piece is
+// its own bytes in its entry (as k_redact<true>; k_win_mask then overwrites the masked ones in place); every
+// other type's stays its token, for a hash type the placeholder k_win_hash overwrites
+template <int WT = WIN_TILE, bool SRC = false>
 __global__ __launch_bounds__(REDACT_BLOCK) void k_win_redact(const RulesDev R, const WinRing W, const WinBatch B,
                                                              const pii_span* __restrict__ wfd,
                                                              const uint64_t* __restrict__ fbase,
@@ -4670,7 +4687,9 @@ __global__ __launch_bounds__(REDACT_BLOCK) void k_win_redact(const RulesDev R, c
                     po += Fi.start - pin;
                     const uint32_t t0 = R.tok_off[Fi.info_type];
                     s_pout[pb] = po;
-                    s_psrc[pb] = (uint64_t)(uintptr_t)(R.tok_bytes + t0);
+                    s_psrc[pb] = SRC && (R.tok_len[Fi.info_type] & XF_SAME_LEN)
+                                     ? src + Fi.start
+                                     : (uint64_t)(uintptr_t)(R.tok_bytes + t0);
                     ++pb;
                     po += out_len(R.tok_len, Fi.info_type, Fi.end - Fi.start);
                     pin = Fi.end;
@@ -4703,9 +4722,196 @@ __global__ __launch_bounds__(REDACT_BLOCK) void k_win_redact(const RulesDev R, c
             const uint32_t nfi = n_wfind[uu];
             uint8_t* dst = out + out_offs[uu];
             const uint32_t olen = (uint32_t)(out_offs[uu + 1] - out_offs[uu]);
-            for (uint32_t rel = lane; rel < olen; rel += 64) dst[rel] = win_byte_slow(R, W, B, iu, F, nfi, rel);
+            for (uint32_t rel = lane; rel < olen; rel += 64) dst[rel] = win_byte_slow<SRC>(R, W, B, iu, F, nfi, rel);
         }
     }
+}
+
+// The post-passes of an engine enabled with PII_WINDOW_XF, after k_win_redact<WT, SRC> and before the ring
+// commit (the windows still read the rings as the call found them): one thread per window finding of the
+// call, si < wspan_offs[n_utt] in the order of the spans.  Its window is the last u with wspan_offs[u] <= si
+// (binary search), its record wfd[fbase[u] + k], its output position out_offs[u] + wpos[fbase[u] + k]
+// (k_win_pos), and its bytes lie in the one entry that holds its start: a ring entry, a batch
+// predecessor or the row itself (win_at), since no finding crosses a "\n".  Nothing but the finding's own
+// output range is written: in_len bytes by k_win_mask, 44 by k_win_hash.
+// k_win_pos, one thread per window like k_win_select, which summed the same deltas for wout_len: wpos,
+// indexed like wfd, takes each finding's output position relative to its window's output (its start + the
+// length deltas of the window's earlier findings), so that no post-pass thread walks its predecessors.
+__global__ __launch_bounds__(256) void k_win_pos(const RulesDev R, const pii_span* __restrict__ wfd,
+                                                 const uint64_t* __restrict__ fbase,
+                                                 const uint32_t* __restrict__ n_wfind, uint32_t n_utt,
+                                                 const uint32_t* __restrict__ err, uint32_t* __restrict__ wpos) {
+    if (*err != 0) return;
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n_utt) return;
+    const pii_span* F = wfd + fbase[u];
+    uint32_t* P = wpos + fbase[u];
+    const uint32_t nf = n_wfind[u];
+    int delta = 0;
+    for (uint32_t k = 0; k < nf; ++k) {
+        const uint32_t s = F[k].start, len = F[k].end - s;
+        P[k] = (uint32_t)((int)s + delta);
+        delta += (int)out_len(R.tok_len, F[k].info_type, len) - (int)len;
+    }
+}
+
+struct WinFind {
+    const uint8_t* in;
+    uint8_t* o;
+    uint32_t t;
+    int len;
+};
+template <int KIND>
+__device__ __forceinline__ bool win_find(const uint8_t* __restrict__ xf_kind, const WinRing& W, const WinBatch& B,
+                                         const pii_span* __restrict__ wfd, const uint64_t* __restrict__ fbase,
+                                         const uint64_t* __restrict__ wspan_offs, const uint32_t* __restrict__ wpos,
+                                         const uint64_t* __restrict__ out_offs, uint8_t* __restrict__ out,
+                                         WinFind& r) {
+    r.in = nullptr;
+    const uint64_t si = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (si >= wspan_offs[B.n_utt]) return false;
+    uint32_t lo = 0, hi = B.n_utt - 1;                  // last window whose first span is at or before si
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (wspan_offs[mid] <= si) lo = mid;
+        else hi = mid - 1;
+    }
+    const uint32_t u = lo;
+    const uint64_t fi = fbase[u] + (si - wspan_offs[u]);
+    const pii_span F = wfd[fi];
+    if (xf_kind[F.info_type] != KIND) return false;
+    const WinIt it = win_begin(W, B, u);
+    uint32_t oj = 0;
+    for (int j = 0; j < it.nw; ++j) {
+        const WEntry Ej = win_at(W, B, it, j);
+        if (F.start < oj + Ej.len + 1 || j + 1 == it.nw) {
+            r.in = Ej.t + (F.start - oj);
+            break;
+        }
+        oj += Ej.len + 1;
+    }
+    r.o = out + out_offs[u] + wpos[fi];
+    r.t = F.info_type;
+    r.len = (int)(F.end - F.start);
+    return true;
+}
+
+// (k_mask's two loops, stated a second time -- a change to either belongs in both -- over the same state
+// machine, for a finding whose bytes and output win_find located; k_mask itself keeps its code, DESIGN §6b.  The mask words by value: held by reference, the compiler keeps them in
+// scratch memory and indexes the skip set there)
+__device__ __forceinline__ void win_mask_walk(const uint4 m0, const uint2 m1, const uint8_t* in, uint8_t* o,
+                                              const int len) {
+    const uint8_t mc = (uint8_t)(m0.x & 0xffu);
+    const bool rev = ((m0.x >> 8) & 1u) != 0;
+    const uint32_t limit = m0.y ? m0.y : 0xffffffffu;
+    uint32_t masked = 0;
+    bool cur = false;                            // the code point being walked is masked
+    auto step = [&](uint32_t b, int i, bool newcp) -> bool {
+        return mask_step(m0, m1, mc, limit, masked, cur, o, b, i, newcp);
+    };
+    if (!rev) {
+        for (int j = 0; j < len; j += 16) {
+            const int n = len - j < 16 ? len - j : 16;
+            uint4 w = load16(in + j, 0, n);
+            for (int k = 0; k < n; ++k) {
+                const uint32_t b = w.x & 0xffu;
+                if (!step(b, j + k, (b & 0xC0u) != 0x80u || j + k == 0)) return;
+                shr8(w);
+            }
+        }
+    } else {
+        bool newcp = true;                       // the byte after this one starts a code point (or is the end)
+        for (int j = len; j > 0; j -= 16) {
+            const int w0 = j - 16, klo = w0 < 0 ? -w0 : 0;      // window [w0, j), its bytes klo .. 15 in the span
+            uint4 w = load16(in + w0, klo, 16);
+            for (int k = 15; k >= klo; --k) {
+                const uint32_t b = w.w >> 24;
+                if (!step(b, w0 + k, newcp)) return;
+                newcp = (b & 0xC0u) != 0x80u;
+                w.w = (w.w << 8) | (w.z >> 24);
+                w.z = (w.z << 8) | (w.y >> 24);
+                w.y = (w.y << 8) | (w.x >> 24);
+                w.x <<= 8;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_win_mask(const RulesDev R, const WinRing W, const WinBatch B,
+                                                  const pii_span* __restrict__ wfd, const uint64_t* __restrict__ fbase,
+                                                  const uint64_t* __restrict__ wspan_offs,
+                                                  const uint32_t* __restrict__ wpos,
+                                                  const uint64_t* __restrict__ out_offs,
+                                                  const uint32_t* __restrict__ err, uint8_t* __restrict__ out) {
+    if (*err != 0) return;
+    WinFind f;
+    if (!win_find<PII_XF_MASK>(R.xf_kind, W, B, wfd, fbase, wspan_offs, wpos, out_offs, out, f)) return;
+    const uint4 m0 = *reinterpret_cast<const uint4*>(R.xf_mask + (size_t)f.t * XF_MASK_WORDS);
+    const uint2 m1 = *reinterpret_cast<const uint2*>(R.xf_mask + (size_t)f.t * XF_MASK_WORDS + 4);
+    win_mask_walk(m0, m1, f.in, f.o, f.len);
+}
+
+__global__ __launch_bounds__(HASH_BLOCK) void k_win_hash(const uint8_t* __restrict__ xf_kind,
+                                                         const uint32_t* __restrict__ hash_key,
+                                                         const uint32_t* __restrict__ hash_mid, const WinRing W,
+                                                         const WinBatch B, const pii_span* __restrict__ wfd,
+                                                         const uint64_t* __restrict__ fbase,
+                                                         const uint64_t* __restrict__ wspan_offs,
+                                                         const uint32_t* __restrict__ wpos,
+                                                         const uint64_t* __restrict__ out_offs,
+                                                         const uint32_t* __restrict__ err, uint8_t* __restrict__ out) {
+    if (*err != 0) return;
+    WinFind f;
+    if (!win_find<PII_XF_HASH>(xf_kind, W, B, wfd, fbase, wspan_offs, wpos, out_offs, out, f)) return;
+    // (k_hash's padding and inner / outer framing, stated a second time -- a change to either belongs in
+    // both -- over the same primitives, load16, sha256_compress, b64_store, for a finding whose bytes and
+    // output were located above; k_hash itself keeps its code)
+    const uint32_t* mid = hash_mid + (size_t)hash_key[f.t] * XF_HASH_KEY_WORDS;
+    const uint8_t* in = f.in;
+    const int len = f.len;
+    uint32_t h[8], w[16];
+    {
+        const uint4 m0 = *reinterpret_cast<const uint4*>(mid), m1 = *reinterpret_cast<const uint4*>(mid + 4);
+        h[0] = m0.x, h[1] = m0.y, h[2] = m0.z, h[3] = m0.w, h[4] = m1.x, h[5] = m1.y, h[6] = m1.z, h[7] = m1.w;
+    }
+    for (int base = 0;; base += 64) {
+        const int rem = len - base;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int n = rem - 16 * q;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (n > 0) v = load16(in + base + 16 * q, 0, n < 16 ? n : 16);
+            const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int m = n - 4 * k;
+                uint32_t u = x[k] & bytemask(m);
+                if (m >= 0 && m < 4) u |= 0x80u << (8 * m);
+                w[4 * q + k] = __builtin_bswap32(u);
+            }
+        }
+        const bool last = rem <= 55;
+        if (last) {
+            w[14] = 0;
+            w[15] = (64u + (uint32_t)len) * 8u;
+        }
+        sha256_compress(h, w);
+        if (last) break;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = h[i];
+    w[8] = 0x80000000u;
+#pragma unroll
+    for (int i = 9; i < 15; ++i) w[i] = 0;
+    w[15] = 96u * 8u;
+    {
+        const uint4 m0 = *reinterpret_cast<const uint4*>(mid + 8), m1 = *reinterpret_cast<const uint4*>(mid + 12);
+        h[0] = m0.x, h[1] = m0.y, h[2] = m0.z, h[3] = m0.w, h[4] = m1.x, h[5] = m1.y, h[6] = m1.z, h[7] = m1.w;
+    }
+    sha256_compress(h, w);
+    const uint32_t d[9] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], 0u};
+    b64_store<0>(d, f.o);
+    f.o[43] = '=';
 }
 
 // after a successful call: the planned rows enter the rings (16 threads per row copy the resident
@@ -5051,6 +5257,10 @@ struct pii_engine {
     uint32_t wcap_utt = 0;
     pii_span* wfd = nullptr;
     uint64_t wfd_cap = 0;
+    // ... of an engine enabled with PII_WINDOW_XF whose rules hold a mask or a hash type (win_xpos): the
+    // findings' output positions (k_win_pos), indexed like wfd
+    uint32_t* wpos = nullptr;
+    uint64_t wpos_cap = 0;
     // external candidates on the window paths (pii_rescan_window_ext): set by the first such call, from then
     // on the rings may hold external records and the XR kernels run; the rows' merged lists (k_win_ext)
     bool win_ext = false;
@@ -5761,6 +5971,24 @@ int run_pipeline(pii_engine* e, const Call& c, const WinFull* wf = nullptr) {
     return end_call(e, c.st, hist_bytes(e), true);
 }
 
+// the incremental path runs k_win_mask / k_win_hash (only an engine enabled with PII_WINDOW_XF gets here
+// with such rules: any other takes the full re-scan)
+bool win_xpos(const pii_engine* e) { return !e->win_full && (e->xf_mask || e->xf_hash); }
+
+// the window findings arena holds at least `want` records; with win_xpos, so does the position array
+int ensure_window_findings(pii_engine* e, uint64_t want) {
+    int rc;
+    if (e->wfd_cap < want) {
+        if ((rc = grow(e, e->wfd, want))) return rc;
+        e->wfd_cap = want;
+    }
+    if (win_xpos(e) && e->wpos_cap < e->wfd_cap) {
+        if ((rc = grow(e, e->wpos, e->wfd_cap))) return rc;
+        e->wpos_cap = e->wfd_cap;
+    }
+    return PII_OK;
+}
+
 int ensure_window_scratch(pii_engine* e, uint32_t n_utt) {
     int rc;
     if (e->wc_cap < e->pair_cap) {
@@ -5776,12 +6004,7 @@ int ensure_window_scratch(pii_engine* e, uint32_t n_utt) {
             return rc;
         e->wcap_utt = nu;
     }
-    const uint64_t want = std::max<uint64_t>(4096, 4ull * n_utt);
-    if (e->wfd_cap < want) {
-        if ((rc = grow(e, e->wfd, want))) return rc;
-        e->wfd_cap = want;
-    }
-    return PII_OK;
+    return ensure_window_findings(e, std::max<uint64_t>(4096, 4ull * n_utt));
 }
 
 void free_window_tables(WinTables& w) {
@@ -5984,6 +6207,7 @@ int run_window(pii_engine* e, const Call& c) {
     // (a call that carries candidates, with or without scan lanes; any other call launches nothing new)
     if (has_ext && (rc = launch_win_ext(e, c, B))) return rc;
     const bool xr = e->win_ext;          // XR kernels: the rings or the batch may hold external records
+    const bool xp = win_xpos(e);         // k_win_pos, then k_win_mask / k_win_hash after the redaction
     const uint32_t nb = (c.n_utt + 255) / 256;
     if (c.n_utt > 0 && n_chunks > 0 && R.n_hot > 0) {
         // (the image in LDS when it fits beside the halo tables, else read in place)
@@ -6018,8 +6242,23 @@ int run_window(pii_engine* e, const Call& c) {
     if (c.n_utt > 0) {
         if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->kev[2], c.st));
         const uint32_t wt = xr ? WIN_TILE_XR : WIN_TILE;
-        (xr ? k_win_redact<WIN_TILE_XR> : k_win_redact<WIN_TILE>)<<<(c.n_utt + wt - 1) / wt, REDACT_BLOCK, 0, c.st>>>(
+        // (xf_src on this path: the engine was enabled with PII_WINDOW_XF)
+        (e->xf_src ? (xr ? k_win_redact<WIN_TILE_XR, true> : k_win_redact<WIN_TILE, true>)
+                   : (xr ? k_win_redact<WIN_TILE_XR> : k_win_redact<WIN_TILE>))<<<(c.n_utt + wt - 1) / wt, REDACT_BLOCK, 0,
+                                                                                c.st>>>(
             R, W, B, e->wfd, e->wfbase, e->n_wfind, c.out_offs, e->wspan_offs, e->d_err, c.out, c.spans);
+        if (xp) {   // (the host does not know the finding count: no more than the span capacity or the arena)
+            const uint64_t ms = std::min<uint64_t>(c.span_cap, e->wfd_cap);
+            k_win_pos<<<nb, 256, 0, c.st>>>(R, e->wfd, e->wfbase, e->n_wfind, c.n_utt, e->d_err, e->wpos);
+            if (e->xf_mask)
+                k_win_mask<<<(uint32_t)(ms / 256) + 1, 256, 0, c.st>>>(R, W, B, e->wfd, e->wfbase, e->wspan_offs, e->wpos,
+                                                                     c.out_offs, e->d_err, c.out);
+            if (e->xf_hash)
+                k_win_hash<<<(uint32_t)(ms / HASH_BLOCK) + 1, HASH_BLOCK, 0, c.st>>>(
+                    R.xf_kind, e->d_hash_key, e->d_hash_mid, W, B, e->wfd, e->wfbase, e->wspan_offs, e->wpos, c.out_offs,
+                    e->d_err, c.out);
+        }
+        // (the redaction stage with its post-passes, as run_pipeline's covers k_mask and k_hash)
         if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->kev[3], c.st));
         k_win_commit<<<(uint32_t)(((uint64_t)c.n_utt * 16 + 255) / 256), 256, 0, c.st>>>(W, B, e->wnew, e->d_err);
         launch_ctx_commit(e, c.n_utt, c.slot, e->kw, c.ts, c.st);
@@ -6433,6 +6672,10 @@ int pii_reserve(pii_engine* e, uint32_t max_utt, uint64_t max_bytes, uint64_t ma
     if ((rc = ensure_scratch(e, max_utt, max_bytes, (uint32_t)std::min<uint64_t>(lanes, 0xffffffffull))) ||
         (rc = ensure_queues(e, max_bytes)) || (rc = ensure_redact(e, max_spans, max_out)))
         return rc;
+    // (the window calls of an engine with the position array: the per-row arrays and the findings arena too)
+    if (e->win_n && win_xpos(e) &&
+        ((rc = ensure_window_scratch(e, max_utt)) || (rc = ensure_window_findings(e, max_spans))))
+        return rc;
     if (e->lb_cap < LB_MAX_TILES + 64) {      // the look-back scans' tile states (exclusive_scan: two scans)
         if ((rc = grow(e, e->lb_state, 2 * ((size_t)LB_MAX_TILES + 64)))) return rc;
         HIPCHK(hipMemsetAsync(e->lb_state, 0, 2 * ((size_t)LB_MAX_TILES + 64) * 8, e->stream));
@@ -6466,10 +6709,7 @@ int pii_sync(pii_engine* e, uint64_t totals[3]) {
             }
             if ((rc = grow_pairs(e, std::max(need, e->pair_cap)))) return rc;
             e->pair_cap = std::max(need, e->pair_cap);
-            if (e->last_kind == 1 && need_wf > e->wfd_cap) {
-                if ((rc = grow(e, e->wfd, need_wf))) return rc;
-                e->wfd_cap = need_wf;
-            }
+            if (e->last_kind == 1 && (rc = ensure_window_findings(e, need_wf))) return rc;
             if (e->excl_ran) {      // k_exclude's occurrence list: its count pass left the exact need (0 if it did not run)
                 uint64_t need_x = 0;
                 HIPCHK(hipMemcpy(&need_x, e->xbase + 2ull * e->last_lanes, sizeof(need_x), hipMemcpyDeviceToHost));
@@ -6746,7 +6986,7 @@ int pii_scan_redact_device_ext(pii_engine* e, const uint8_t* d_bytes, const uint
 
 int pii_window_enable_ex(pii_engine* e, uint32_t window_n, uint32_t slot_bytes, uint32_t flags) {
     if (!e || window_n == 0 || window_n > WN_MAX || slot_bytes < 64 || slot_bytes % 16 ||
-        (flags & ~(uint32_t)PII_WINDOW_FULL))
+        (flags & ~(uint32_t)(PII_WINDOW_FULL | PII_WINDOW_XF)))
         return PII_E_ARG;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -6764,9 +7004,11 @@ int pii_window_enable_ex(pii_engine* e, uint32_t window_n, uint32_t slot_bytes, 
     // (config 5: the groups' merged pair queue, candidate lists past LIVE patterns spilled like
     // k_select's) and tables past LDS (read in place); any other rule set re-scans the joined windows
     // in full
-    // (a mask / keep type's output comes from the text, a hash type's is computed from it: the window
-    // redaction kernel's pieces do not produce either, the scan+redact pipeline the full re-scan runs does)
-    e->win_full = (flags & PII_WINDOW_FULL) || !e->window_ok || e->xf_src || e->xf_hash;
+    // (a mask / keep type's output comes from the text, a hash type's is computed from it: the scan+redact
+    // pipeline the full re-scan runs produces both; with PII_WINDOW_XF the incremental path does, by
+    // k_win_redact<WT, true>, k_win_mask and k_win_hash)
+    const bool xf_full = !(flags & PII_WINDOW_XF) && (e->xf_src || e->xf_hash);
+    e->win_full = (flags & PII_WINDOW_FULL) || !e->window_ok || xf_full;
     e->win_n = window_n;
     e->win_slot_bytes = slot_bytes;
     e->win_ext = false;                  // (fresh rings)

@@ -295,14 +295,22 @@ int pii_exclusion_mode(struct pii_engine* e);
  * re-scan -- the ring then keeps the raw text, every row's "\n"-joined window is materialised in HBM
  * and run through the scan+redact pipeline (one host wait per call for the joined size).  Rules with a
  * PII_XF_MASK, PII_XF_KEEP or PII_XF_HASH type (output bytes taken or computed from the text) also
- * take the FULL re-scan. */
+ * take the FULL re-scan, unless the window is enabled with PII_WINDOW_XF: then
+ *     full = (flags & PII_WINDOW_FULL) || the rules are not incremental ('\n'-consuming detector, general
+ *            or text exclusion rules)
+ * and such rules run incrementally too: a mask / keep finding's bytes are copied from its resident entry,
+ * then one thread per window finding masks its code points or computes its surrogate over the placeholder
+ * (a surrogate is computed again in every window that holds the finding).  Same bytes, spans and offsets as
+ * the FULL re-scan; without the flag nothing changes. */
 #define PII_WINDOW_MAX 8
 #define PII_WINDOW_FULL 1   /* pii_window_enable_ex flag / pii_window_mode result: full re-scan */
+#define PII_WINDOW_XF 2     /* pii_window_enable_ex flag: mask / keep / hash types do not force the full re-scan */
 /* allocate the per-slot window history (n_conv_slots * slot_bytes of HBM); window_n <= PII_WINDOW_MAX,
  * slot_bytes a multiple of 16 (a window must fit: its utterances, each rounded up to 16 B, + 16 B per
  * resident candidate, external ones (pii_rescan_window_ext) included) */
 int pii_window_enable(struct pii_engine* e, uint32_t window_n, uint32_t slot_bytes);
-/* the same; flags PII_WINDOW_FULL forces the full re-scan even for rules the incremental path takes */
+/* the same; flags: PII_WINDOW_FULL forces the full re-scan even for rules the incremental path takes (with
+ * or without PII_WINDOW_XF), PII_WINDOW_XF see above; any other bit is PII_E_ARG */
 int pii_window_enable_ex(struct pii_engine* e, uint32_t window_n, uint32_t slot_bytes, uint32_t flags);
 /* PII_WINDOW_FULL or 0 (incremental) for an enabled window, else PII_E_ARG */
 int pii_window_mode(struct pii_engine* e);
