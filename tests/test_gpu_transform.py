@@ -111,6 +111,30 @@ def test_known_answers_external_candidate(k, tmp_path, oracle_cfg):
         eng.close()
 
 
+@pytest.mark.parametrize("which", sorted(X.LONG_MASKS))
+def test_masked_candidate_of_several_windows_at_every_alignment(which, tmp_path, oracle_cfg):
+    """the mask walk past its first 16-byte window: a 68-byte external candidate of 1- to 4-byte code points
+    (X.LONG_NAME; the entry point does not limit a candidate's length) whose code points straddle the
+    window edges of both directions, at each of the 16 alignments of its first byte, masked whole and up to
+    a count that runs out in the second (forward) or third (reverse) window"""
+    E, comp = pkg("engine"), pkg("compiler")
+    prim = X.LONG_MASKS[which]
+    cfg = X.with_block([{"info_types": [{"name": "PERSON_NAME"}], "primitive_transformation": prim}])
+    eng = E.Engine(comp.compile_default(X.write(tmp_path, "long", cfg)).blob, device=0, n_conv_slots=16)
+    try:
+        pn = eng.type_names.index("PERSON_NAME")
+        assert eng.type_transform(pn) == E.PII_XF_MASK
+        texts, spans = X.long_rows()
+        _, offs = E.pack(texts)
+        assert {(int(offs[i]) + s) % 16 for i, (s, _) in enumerate(spans)} == set(range(16))
+        res = _check_host(eng, _rows(texts), oracle_cfg, cfg, [[(s, e, pn, 4)] for s, e in spans])
+        masked = xform_ref.mask(X.LONG_NAME, prim["character_mask_config"])
+        for i, (t, (s, e)) in enumerate(zip(texts, spans)):
+            assert res.text(i) == t[:s] + masked + t[e:], i
+    finally:
+        eng.close()
+
+
 # ------------------------------------------------------------------------------------------ 2 corpus
 @pytest.fixture(scope="module")
 def corpus(oracle_cfg):

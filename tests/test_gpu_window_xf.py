@@ -19,6 +19,7 @@ import pytest
 import window_ext_ref as WR
 import xform_configs as X
 import xform_hash_ref as HR
+import xform_ref
 from conftest import ROOT, pkg
 
 pytestmark = pytest.mark.gpu
@@ -424,21 +425,35 @@ def test_a_later_agent_row_changes_what_the_window_selects(tmp_path):
 
 
 # -------------------------------------------------------------------------------- 7 external candidates
-@pytest.mark.parametrize("which", ["mask_utf8", "mask_reverse", "hash"])
+@pytest.mark.parametrize("which", ["mask_utf8", "mask_reverse", "hash"] + ["long_" + k for k in sorted(X.LONG_MASKS)])
 def test_external_candidates(which, cfgs, oracle_cfg, tmp_path):
+    """long_*: the rows of test_gpu_transform's test_masked_candidate_of_several_windows_at_every_alignment, a
+    68-byte candidate (the entry point does not limit its length) at 16 alignments under X.LONG_MASKS, one row
+    per call; each window is also what the batch path gives for the joined window with the same candidates"""
     from oracle import pii_oracle as O
-    comp = pkg("compiler")
-    prim = {"mask_utf8": X.KNOWN_EXT[0][0], "mask_reverse": X.KNOWN_EXT[1][0], "hash": HR.hash_prim(HR.KEY1)}[which]
-    first = {"mask_utf8": X.KNOWN_EXT[0][1], "mask_reverse": X.KNOWN_EXT[1][1],
-             "hash": b"I am " + HR.JOSE_KEY1 + b" ok"}[which]
+    E, comp = pkg("engine"), pkg("compiler")
+    long = which.startswith("long_")
+    C = O.ROLE_CUSTOMER
+    P = oracle_cfg.type_id["PERSON_NAME"]
+    if long:
+        prim = X.LONG_MASKS[which[5:]]
+        texts, at = X.long_rows()
+        rows = [(4, C, t, 1 + k) for k, t in enumerate(texts)]
+        ext = [[(s, e, P, 4)] for s, e in at]
+        masked = xform_ref.mask(X.LONG_NAME, prim["character_mask_config"])
+        want = [t[:s] + masked + t[e:] for t, (s, e) in zip(texts, at)]
+    else:
+        prim = {"mask_utf8": X.KNOWN_EXT[0][0], "mask_reverse": X.KNOWN_EXT[1][0],
+                "hash": HR.hash_prim(HR.KEY1)}[which]
+        first = {"mask_utf8": X.KNOWN_EXT[0][1], "mask_reverse": X.KNOWN_EXT[1][1],
+                 "hash": b"I am " + HR.JOSE_KEY1 + b" ok"}[which]
+        rows = [(4, C, X.EXT_TEXT, 1)] + [(4, C, b"row %d 212-555-0187" % k, 2 + k) for k in range(5)]
+        ext = [[(X.EXT_SPAN[0], X.EXT_SPAN[1], P, 4)]] + [[] for _ in range(5)]
     cfg = X.with_block([{"info_types": [{"name": "PERSON_NAME"}], "primitive_transformation": prim},
                         {"primitive_transformation": {"replace_with_info_type_config": {}}}])
     blob = comp.compile_default(X.write(tmp_path, "ext_" + which, cfg)).blob
-    C = O.ROLE_CUSTOMER
-    P = oracle_cfg.type_id["PERSON_NAME"]
-    rows = [(4, C, X.EXT_TEXT, 1)] + [(4, C, b"row %d 212-555-0187" % k, 2 + k) for k in range(5)]
-    ext = [[(X.EXT_SPAN[0], X.EXT_SPAN[1], P, 4)]] + [[] for _ in range(5)]
     full, inc = _engine(blob, False, full=True, n_slots=16), _engine(blob, True, n_slots=16)
+    batch = E.Engine(blob, device=0, n_conv_slots=16) if long else None
     try:
         assert (full.window_mode(), inc.window_mode()) == ("full", "incremental")
         ref = _Ref(oracle_cfg)
@@ -447,10 +462,20 @@ def test_external_candidates(which, cfgs, oracle_cfg, tmp_path):
             rf, ri = _call(full, [r], [x]), _call(inc, [r], [x])
             _same(rf, ri, 1)
             _check(ri, w, oracle_cfg, cfg, [r])
-            assert ri.text(0).startswith(first) == (k < 5), k            # five consecutive windows hold the row
+            if not long:
+                assert ri.text(0).startswith(first) == (k < 5), k        # five consecutive windows hold the row
+                continue
+            assert ri.text(0) == b"\n".join(want[max(k - 4, 0):k + 1]), k
+            joined, fs, _ = w[0]
+            assert [f.type_id for f in fs] == [P] * min(k + 1, 5)
+            rb = batch.scan_redact([joined], [4], [C], [r[3]],
+                                   ext=[[(f.start, f.end, f.type_id, f.likelihood) for f in fs]])
+            assert rb.text(0) == ri.text(0) and _spans(rb) == _spans(ri), k
     finally:
         full.close()
         inc.close()
+        if batch:
+            batch.close()
 
 
 # -------------------------------------------------------------------------- 8 nothing committed on failure

@@ -150,6 +150,35 @@ def test_reference_reproduces_the_known_answers(oracle_cfg):
         assert xform_ref.apply_transform(text, fs, names, {}) == red
 
 
+def test_long_name_rows_hold_what_the_gpu_tests_take_them_for(oracle_cfg):
+    """X.long_rows / X.LONG_MASKS: the only finding is the candidate, code points of every length straddle
+    the 16-byte window edges of both walk directions, and the two counts end where their names say"""
+    from oracle import pii_oracle as O
+    name, L = X.LONG_NAME, len(X.LONG_NAME)
+    chars = name.decode()
+    at = np.cumsum([0] + [len(c.encode()) for c in chars])           # code point k = bytes at[k] .. at[k + 1]
+    assert L == 68 and {int(b - a) for a, b in zip(at, at[1:])} == {1, 2, 3, 4} and " " in chars and "-" in chars
+    for edge in (16, 32, L - 16, L - 32, L - 48):
+        assert edge not in at, edge
+    texts, spans = X.long_rows()
+    pn = oracle_cfg.type_names.index("PERSON_NAME")
+    assert [len(t) for t in texts] == [96] * 16 and [s for s, _ in spans] == list(range(16))
+    for t, (s, e) in zip(texts, spans):
+        assert t[s:e] == name and not O.find_pii(t, oracle_cfg)
+        fs = O.find_pii(t, oracle_cfg, extra=[(s, e, pn, 4)])
+        assert [(f.start, f.end, f.type_id) for f in fs] == [(s, e, pn)]
+    star = lambda k: b"*" * int(at[k + 1] - at[k])                   # noqa: E731
+    fwd = xform_ref.mask(name, X.LONG_MASKS["forward_18"]["character_mask_config"])
+    assert fwd == b"#" * int(at[18]) + name[at[18]:] and 16 <= at[17] < at[18] < 32
+    rev = xform_ref.mask(name, X.LONG_MASKS["reverse_21"]["character_mask_config"])
+    kept = [k for k in range(len(chars) - 1, -1, -1) if chars[k] not in " -"][21:]
+    assert rev == b"".join(chars[k].encode() if k in kept or chars[k] in " -" else star(k) for k in range(len(chars)))
+    last, stop = [k for k in range(len(chars)) if chars[k] not in " -" and k not in kept][0], kept[0]
+    assert L - 48 <= at[stop] < at[last] < L - 32                    # the third window from the end
+    assert xform_ref.mask(name, X.LONG_MASKS["forward_all"]["character_mask_config"]) == b"*" * L
+    assert xform_ref.mask(name, X.LONG_MASKS["reverse_all"]["character_mask_config"]) == b"*" * L
+
+
 def test_header_declares_and_library_exports_type_transform():
     E = pkg("engine")
     src = open(os.path.join(ROOT, "include", "pii_engine.h")).read()

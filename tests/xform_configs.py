@@ -55,6 +55,32 @@ KNOWN_EXT = [
            characters_to_ignore=[{"characters_to_skip": " "}]), "I am José Nú**** ok".encode()),
 ]
 
+# A masked finding of several 16-byte windows of the mask walk (windows count from the finding's first
+# byte, or from its last when reverse_order): one PERSON_NAME external candidate of 68 bytes, 1- to 4-byte
+# code points, spaces and '-'.  A code point straddles the window edges at bytes 16 and 32 and, from the end,
+# at 52, 36 and 20.  The external-candidate entry points do not limit a candidate's length.
+LONG_NAME = "Zoë-Renée 李小龍 Ñandú 𝒜𝓁𝒾 Łukasz-Ødegård 𐍈bé".encode()
+LONG_PREFIX = b"it is me, I am "                 # its last 0 .. 15 bytes precede the name
+LONG_SUFFIX = b" ok, that is all there is to it"
+LONG_MASKS = {
+    "forward_all": _mask(masking_character="*"),
+    "forward_18": _mask(masking_character="#", number_to_mask=18),                # ends at byte 27: second window
+    "reverse_all": _mask(masking_character="*", reverse_order=True),
+    "reverse_21": _mask(masking_character="*", number_to_mask=21, reverse_order=True,     # ends at byte 26: third
+                        characters_to_ignore=[{"characters_to_skip": " -"}]),
+}
+
+
+def long_rows():
+    """16 rows of 96 bytes -> (texts, [(start, end)] of the name in each): 0 .. 15 bytes before the name, so
+    that in a batch packed back to back it starts at each of the 16 byte offsets modulo 16 once"""
+    texts, spans = [], []
+    for a in range(16):
+        row = LONG_PREFIX[len(LONG_PREFIX) - a:] + LONG_NAME
+        texts.append(row + LONG_SUFFIX[:96 - len(row)])
+        spans.append((a, a + len(LONG_NAME)))
+    return texts, spans
+
 
 def shipped() -> dict:
     with open(os.path.join(pkg("compiler").RULES_DIR, "dlp_config.json")) as f:
