@@ -338,8 +338,8 @@ __device__ __attribute__((noinline)) uint64_t block_bits_slow(const Geo g, uint3
 // A wavefront of k_scan runs as long as its longest lane (a lane is ~1 KiB of WHOLE utterances, so
 // lengths spread over ~0.5-2 KiB: in batch order a wavefront's lanes are only ~80% busy).  The scan
 // therefore takes its lanes in order of decreasing length: a counting sort on 32-byte length buckets
-// gives slot -> lane (lane_perm) and lane -> slot (lane_pos); k_lane_bits writes each lane's start
-// words at its slot, so the scan's word loads stay coalesced.  The order is not deterministic (block
+// gives slot -> lane (lane_perm) and lane -> slot; each lane's start words are written at its slot
+// (by k_lane_place itself, or by k_lane_bits through lane_pos), so the scan's word loads stay coalesced.  The order is not deterministic (block
 // reservations race) but only the thread mapping depends on it: every lane's events, counts and
 // arena are the same.
 constexpr int LANE_NB = 128;                       // length buckets: 0 = longest (>= 127*32 B)
@@ -368,50 +368,6 @@ __global__ __launch_bounds__(256) void k_lane_count(const Geo g, uint32_t* __res
     __syncthreads();
     for (int i = threadIdx.x; i < LANE_NB; i += blockDim.x)
         if (h[i]) atomicAdd(&bucket_cnt[i], h[i]);
-}
-
-// bucket_cnt[0..NB) = counts (k_lane_count), bucket_cnt[NB..2NB) = reservation cursors (zeroed)
-__global__ __launch_bounds__(256) void k_lane_place(const Geo g, uint32_t* __restrict__ bucket_cnt,
-                                                    uint32_t* __restrict__ lane_perm, uint32_t* __restrict__ lane_pos) {
-    constexpr int PER = LANE_SORT_CHUNK / 256;
-    __shared__ uint32_t base[LANE_NB], h[LANE_NB];
-    if (threadIdx.x < 64) {                        // exclusive prefix of the counts, one wavefront
-        uint32_t run = 0;
-        for (int k = 0; k < LANE_NB; k += 64) {
-            const uint32_t v = bucket_cnt[k + threadIdx.x];
-            uint32_t incl = v;
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = __shfl_up(incl, d);
-                if ((int)threadIdx.x >= d) incl += o;
-            }
-            base[k + threadIdx.x] = run + incl - v;
-            run += __shfl(incl, 63);
-        }
-    }
-    for (int i = threadIdx.x; i < LANE_NB; i += blockDim.x) h[i] = 0;
-    __syncthreads();
-    const uint32_t c0 = blockIdx.x * LANE_SORT_CHUNK;
-    uint32_t bk[PER], rk[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const uint32_t c = c0 + j * 256 + threadIdx.x;
-        bk[j] = 0;
-        if (c < g.n_chunks) bk[j] = lane_bucket(g, c);
-        rk[j] = c < g.n_chunks ? atomicAdd(&h[bk[j]], 1u) : 0u;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < LANE_NB; i += blockDim.x)
-        if (h[i]) base[i] += atomicAdd(&bucket_cnt[LANE_NB + i], h[i]);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const uint32_t c = c0 + j * 256 + threadIdx.x;
-        if (c < g.n_chunks) {
-            const uint32_t t = base[bk[j]] + rk[j];
-            lane_perm[t] = c;
-            lane_pos[c] = t;
-        }
-    }
 }
 
 typedef const __attribute__((address_space(3))) uint16_t lds_u16_t;
@@ -490,26 +446,15 @@ struct WaveRows {
     }
 };
 
-// one thread per lane; the wavefront stages its utterance offsets in LDS first (coalesced loads)
-__global__ __launch_bounds__(256) void k_lane_bits(const Geo g, const uint32_t* __restrict__ lane_pos,
-                                                   uint64_t* __restrict__ words) {
-    // (16 KiB of LDS per workgroup leaves the kernel at its register occupancy, 7 waves/SIMD)
-    __shared__ uint16_t s_off[4][WROWS_CAP];
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t cw0 = c - lane;
-    const uint32_t cw1 = min(cw0 + 64, g.n_chunks);
-    WaveRows W;
-    if (cw0 < g.n_chunks) W.stage(g, cw0, cw1, lane, s_off[wv]);
-    __syncthreads();
-    if (c >= g.n_chunks) return;
+// lane c's start words, written at its scan slot (W: the rows of the wavefront's 64 lanes, staged)
+__device__ __forceinline__ void lane_words(const Geo& g, const WaveRows& W, uint32_t c, uint32_t slot,
+                                           uint64_t* __restrict__ words) {
     auto uoff = [&](int64_t u) { return W.off(g, (uint32_t)u); };
     const Lane L = g_lane(g, c);
     const uint32_t top = L.hi;
     if (top <= L.lo) return;
     const int64_t b_hi = ((int64_t)top - 1 + g.r0) >> 6, b_lo = ((int64_t)L.lo + g.r0) >> 6;
     const int64_t nw = min<int64_t>(b_hi - b_lo + 1, LANE_WORDS);
-    const uint32_t slot = lane_pos[c];
     const int64_t vmin = (int64_t)L.u0 + (L.clo ? 1 : 0);
     int64_t v = (int64_t)L.u1 - 1;
     int64_t sv = v >= vmin ? uoff(v) : 0;
@@ -523,6 +468,90 @@ __global__ __launch_bounds__(256) void k_lane_bits(const Geo g, const uint32_t* 
             if (v >= vmin) sv = uoff(v);
         }
         words[(uint64_t)i * g.n_chunks + slot] = bits;
+    }
+}
+
+// one thread per lane; the wavefront stages its utterance offsets in LDS first (coalesced loads)
+__global__ __launch_bounds__(256) void k_lane_bits(const Geo g, const uint32_t* __restrict__ lane_pos,
+                                                   uint64_t* __restrict__ words) {
+    // (16 KiB of LDS per workgroup leaves the kernel at its register occupancy, 7 waves/SIMD)
+    __shared__ uint16_t s_off[4][WROWS_CAP];
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t cw0 = c - lane;
+    const uint32_t cw1 = min(cw0 + 64, g.n_chunks);
+    WaveRows W;
+    if (cw0 < g.n_chunks) W.stage(g, cw0, cw1, lane, s_off[wv]);
+    __syncthreads();
+    if (c >= g.n_chunks) return;
+    lane_words(g, W, c, lane_pos[c], words);
+}
+
+// bucket_cnt[0..NB) = counts (k_lane_count), bucket_cnt[NB..2NB) = reservation cursors (zeroed).
+// BITS: the threads that placed a lane write its start words too (k_lane_bits' work: no lane_pos
+// round trip, one launch less).  Thread x's j-th lane is c0 + NT j + x, so in every round j a
+// wavefront holds 64 address-consecutive lanes, as a wavefront of k_lane_bits does, and stages their
+// rows in its own part of s_off; staging and use stay inside the wavefront, so the rounds need no
+// workgroup barrier (LDS operations of one wavefront complete in order).  It runs a workgroup's 1024
+// lanes on 1024 threads (PLACE_BITS_NT): with 256, four rounds deep, a CU held 16 wavefronts where
+// k_lane_bits holds 32, and the kernel took 118 us where k_lane_place and k_lane_bits took 103.
+constexpr int PLACE_BITS_NT = 1024;
+template <bool BITS, int NT>
+__global__ __launch_bounds__(NT) void k_lane_place(const Geo g, uint32_t* __restrict__ bucket_cnt,
+                                                   uint32_t* __restrict__ lane_perm, uint32_t* __restrict__ lane_pos,
+                                                   uint64_t* __restrict__ words) {
+    constexpr int PER = LANE_SORT_CHUNK / NT;
+    static_assert(PER * NT == (int)LANE_SORT_CHUNK, "whole rounds");
+    __shared__ uint32_t base[LANE_NB], h[LANE_NB];
+    __shared__ uint16_t s_off[BITS ? NT / 64 : 1][BITS ? WROWS_CAP : 1];
+    if (threadIdx.x < 64) {                        // exclusive prefix of the counts, one wavefront
+        uint32_t run = 0;
+        for (int k = 0; k < LANE_NB; k += 64) {
+            const uint32_t v = bucket_cnt[k + threadIdx.x];
+            uint32_t incl = v;
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t o = __shfl_up(incl, d);
+                if ((int)threadIdx.x >= d) incl += o;
+            }
+            base[k + threadIdx.x] = run + incl - v;
+            run += __shfl(incl, 63);
+        }
+    }
+    for (int i = threadIdx.x; i < LANE_NB; i += blockDim.x) h[i] = 0;
+    __syncthreads();
+    const uint32_t c0 = blockIdx.x * LANE_SORT_CHUNK;
+    uint32_t bk[PER], rk[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const uint32_t c = c0 + j * NT + threadIdx.x;
+        bk[j] = 0;
+        if (c < g.n_chunks) bk[j] = lane_bucket(g, c);
+        rk[j] = c < g.n_chunks ? atomicAdd(&h[bk[j]], 1u) : 0u;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < LANE_NB; i += blockDim.x)
+        if (h[i]) base[i] += atomicAdd(&bucket_cnt[LANE_NB + i], h[i]);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const uint32_t c = c0 + j * NT + threadIdx.x;
+        const uint32_t t = base[bk[j]] + rk[j];
+        if (c < g.n_chunks) {
+            lane_perm[t] = c;
+            if (!BITS) lane_pos[c] = t;
+        }
+        if (BITS) {
+            const uint32_t cw0 = c - lane;
+            if (cw0 >= g.n_chunks) break;            // (the whole wavefront: no lanes from here on)
+            WaveRows W;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");       // the last round's reads of s_off
+            __builtin_amdgcn_wave_barrier();
+            W.stage(g, cw0, min(cw0 + 64, g.n_chunks), lane, s_off[wv]);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (c < g.n_chunks) lane_words(g, W, c, t, words);
+        }
     }
 }
 
@@ -4824,6 +4853,7 @@ struct EngineKnobs {
     uint32_t merge_cap = MERGE_EVW;    // PII_MERGE_CAP: k_pairs_merge: events a wavefront stages (0: walk)
     bool scan_count = true;            // PII_SCAN_COUNT=0: the count pass counts each lane's pairs, not the scan kernels
     bool long_gate = true;             // PII_LONG_GATE=0: every call launches the long-row kernels
+    bool lane_prep = true;             // PII_LANE_PREP=0: k_lane_bits writes the start words, not k_lane_place
     bool scan_ilv = true;              // PII_SCAN_ILV: k_scan grids of <= n_cu workgroups deal wavefronts round-robin
     uint32_t win_long = 0;             // PII_WIN_LONG: incremental re-scan: rows longer than this many lanes are cut (0: never)
     uint32_t halo_items = HALO_ITEMS;  // PII_HALO_ITEMS: k_win_halo's item list per workgroup (tests)
@@ -5398,6 +5428,9 @@ int launch_front(pii_engine* e, const Call& c, const CallGeo& cg, const Front& f
     const RulesDev& R = e->R;
     e->epoch += 1;
     const bool long_k = long_kernels && e->long_min != NO_CUTS;
+    // One SCAN group: k_lane_place writes the start words at the slots it hands out, and k_lane_bits is
+    // not launched (several groups keep it: not measured there).  PII_LANE_PREP=0: k_lane_bits always.
+    const bool place_bits = e->k.lane_prep && e->n_sg == 1;
     // counter block (a second pass over the call starts from the first pass's), lane buckets, and the
     // histogram if pii_histogram_reset was called since the last call
     k_begin<<<1, 256, 0, c.st>>>(e->d_err, err_init, e->lane_bkt, n_chunks > 0 ? 2u * LANE_NB : 0u, e->hist,
@@ -5418,7 +5451,9 @@ int launch_front(pii_engine* e, const Call& c, const CallGeo& cg, const Front& f
             Geo g0 = g;
             g0.lanes = nullptr;
             k_lane_count<<<nsb, 256, 0, c.st>>>(g0, e->lane_bkt, e->lane_geo);
-            k_lane_place<<<nsb, 256, 0, c.st>>>(g, e->lane_bkt, e->lane_perm, e->lane_pos);
+            if (place_bits)
+                k_lane_place<true, PLACE_BITS_NT><<<nsb, PLACE_BITS_NT, 0, c.st>>>(g, e->lane_bkt, e->lane_perm, nullptr, e->bnd);
+            else k_lane_place<false, 256><<<nsb, 256, 0, c.st>>>(g, e->lane_bkt, e->lane_perm, e->lane_pos, nullptr);
             // one pass per SCAN group (one for the shipped rules): scan, then the stitching; the
             // utterance-start words are written once.  Several groups: group q on stream q mod
             // SCAN_STREAMS (forked after the words, joined before the pairs), so one pass's tail -- the
@@ -5438,7 +5473,7 @@ int launch_front(pii_engine* e, const Call& c, const CallGeo& cg, const Front& f
                 uint32_t* cq = e->lane_cnt + (uint64_t)q * e->cap_lanes;
                 uint32_t* stq = e->lane_st + 2ull * q * e->cap_lanes;
                 if (q == 0) {
-                    k_lane_bits<<<(n_chunks + 255) / 256, 256, 0, c.st>>>(g, e->lane_pos, e->bnd);
+                    if (!place_bits) k_lane_bits<<<(n_chunks + 255) / 256, 256, 0, c.st>>>(g, e->lane_pos, e->bnd);
                     if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->kev[0], c.st));
                     if (two) {
                         HIPCHK(hipEventRecord(e->ev_fork, c.st));
@@ -6060,6 +6095,7 @@ EngineKnobs read_knobs() {
     k.merge_cap = (uint32_t)env("PII_MERGE_CAP", MERGE_EVW, 0, MERGE_EVW);
     k.scan_count = env("PII_SCAN_COUNT", 1, -ANY, ANY) != 0;
     k.long_gate = env("PII_LONG_GATE", 1, -ANY, ANY) != 0;
+    k.lane_prep = env("PII_LANE_PREP", 1, -ANY, ANY) != 0;
     k.scan_ilv = env("PII_SCAN_ILV", 1, -ANY, ANY) != 0;
     k.win_long = (uint32_t)env("PII_WIN_LONG", 0, 0, 64);
     k.halo_items = (uint32_t)env("PII_HALO_ITEMS", HALO_ITEMS, 0, HALO_ITEMS);
