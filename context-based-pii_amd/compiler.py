@@ -1577,6 +1577,7 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET, text_exclusions:
     general = (any(i & XG_PARTIAL for i in excl_ids) or ne > NE_MAX or bool(excluder_types & excluded_types)
                or bool(xt_rules))
     xg_sections = OrderedDict()
+    window_xg_ok = 0
     if general:
         if ne > NX_MAX:
             raise RuleError(f"{ne} excluder patterns (more than {NX_MAX})")
@@ -1588,7 +1589,10 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET, text_exclusions:
         excl_off = np.zeros(V * T + 1, dtype=np.uint32)
         excl_ids = []
         exidx = np.full(P, 0xFF, dtype=np.uint8)
-        window_ok = 0          # k_win_select's streaming exclusion cannot look ahead: windows re-scan in FULL
+        # k_win_select's streaming exclusion cannot look ahead: windows re-scan in FULL, unless the window is
+        # enabled with PII_WINDOW_XG and nothing but these rules took window_ok (window_xg_ok, meta[15])
+        window_xg_ok = window_ok
+        window_ok = 0
     if xt_rules:
         # text exclusion rules: per-(variant, type) rule lists, per rule (kind, window_before, window_after, 0)
         # and a HOT-form automaton in a pool of its own -- FULL / INVERSE: of \A(?:pattern)\Z, accepting
@@ -1667,7 +1671,7 @@ def compile_rules(rules: Rules, scan_budget: int = SCAN_BUDGET, text_exclusions:
     meta = np.array([P, G, T, V,
                      scan_d.n_states, scan_d.n_classes + 1, scan_d.start,
                      scan_k.n_states, scan_k.n_classes + 1, scan_k.start,
-                     len(hot_rules), min_len, scan_budget, window_ok, len(groups) - 1, 0], dtype=np.int64)
+                     len(hot_rules), min_len, scan_budget, window_ok, len(groups) - 1, window_xg_ok], dtype=np.int64)
     S = OrderedDict()
     S["meta"] = meta
     S["scan.cmap2"] = cmap2

@@ -4248,18 +4248,228 @@ __global__ __launch_bounds__(256) void k_win_plan(const WinRing W, const WinBatc
     bound[u] = b;
 }
 
+// The likelihood of resident candidate C = [s, e) of entry j (window offset oj, length elen) of window `it`
+// (nw entries, WL bytes) under the rule list `key` = variant * T + type: the pattern's own, then every
+// hotword rule of the list -- the resident proximity bits where they are known (at the window start the
+// clipped ones, with >= need predecessors the ones over the halo), else, or for rules past WHOT_BITS, a
+// re-run over the joined window.  k_win_lik calls it; k_win_select keeps the same loop written out (see there).
+struct WinLikTabs {
+    Pool pool;
+    const int32_t* hdesc;
+    const int32_t* hrule;
+    const uint8_t* dlik;
+    const void* rix;
+    uint32_t rw;
+    const uint32_t* rloff;
+    const uint16_t* rids;
+};
+__device__ __forceinline__ int win_cand_lik(const WinLikTabs& L, const WinRing& W, const WinBatch& B, const WinIt& it,
+                                            const WCand& C, int s, int e, int j, int nw, uint32_t oj, uint32_t elen,
+                                            uint32_t WL, uint32_t key) {
+    int lik = L.dlik[C.p];
+    uint32_t r0, r1;
+    list_range<true>(L.rix, L.rw, L.rloff, key, r0, r1);
+    const bool known = C.need == 0 || j == 0 || j >= (int)C.need;
+    const uint32_t bits = (C.need == 0 || j == 0) ? C.hot : C.hotx;
+    for (uint32_t q = r0; q < r1; ++q) {
+        const int h = L.rids[q];
+        const int wb = L.hrule[4 * h], wa = L.hrule[4 * h + 1];
+        const bool ca = wa > 0 && (uint32_t)(e + wa) > elen && j + 1 < nw;   // reaches the next utterance
+        const uint32_t ps = oj + (uint32_t)s, pe = oj + (uint32_t)e;
+        bool hit;
+        if (h < WHOT_BITS && known) {
+            hit = (bits >> h) & 1u;
+            if (!hit && ca) hit = hot_run_win(L.pool, L.hdesc + 8 * h, W, B, it, pe, min(WL, pe + (uint32_t)wa));
+        } else {
+            hit = wb > 0 && hot_run_win(L.pool, L.hdesc + 8 * h, W, B, it, ps > (uint32_t)wb ? ps - wb : 0u, ps);
+            if (!hit && wa > 0) hit = hot_run_win(L.pool, L.hdesc + 8 * h, W, B, it, pe, min(WL, pe + (uint32_t)wa));
+        }
+        if (hit) lik = hot_rule_apply(lik, L.hrule + 4 * h);
+    }
+    return lik;
+}
+
+// ---- general and text exclusion rules on the incremental path (an engine enabled with PII_WINDOW_XG whose
+// rules are PII_EXCLUSION_GENERAL; no other engine launches these or allocates wlik).  An excluder
+// occurrence is a matched pair that passed finditer and its validator: a resident candidate of its
+// utterance, and candidates of different utterances never overlap.  So a window decides per entry, over
+// the entry's candidates c_0 .. c_{n-1}:
+//   lik_k        win_cand_lik under the window's variant v
+//   cand_k       ven[v, type_k] && lik_k >= vmin[v]        (an excluder must itself be a candidate)
+//   text_drop_k  cand_k && a rule of the xt list of (v, type_k) drops it: SEARCH / FULL / INVERSE over the
+//                entry's own bytes [s, e), HOTWORD over the joined window (across the "\n" joins, as
+//                k_excl_text over the FULL path's joined text)
+//   type_drop_k  cand_k && some g != k of the same entry has cand_g, type_g in the xg list of (v, type_k),
+//                and overlaps (XG_PARTIAL) or contains c_k; g from the unfiltered list (dropped or not)
+// and c_k competes in StartPicker iff cand_k && !type_drop_k && !text_drop_k.  External records neither
+// exclude nor are excluded.  wlik holds one byte per window candidate, indexed like the findings arena
+// (wfbase[u] + the candidate's running index in its window; k_win_plan's bound is that count):
+constexpr uint8_t WLIK_LIK = 0x3f;      // the likelihood; WLIK_LIK itself: not a candidate
+constexpr uint8_t WLIK_TYPE = 0x40;     // type_drop (k_win_xmark; readers of "is g a candidate" mask it off)
+constexpr uint8_t WLIK_TEXT = 0x80;     // text_drop: kept apart from the likelihood, it still excludes
+
+// k_win_lik: one thread per (window, entry), W.N threads per window: lik, cand and text_drop of the entry's
+// candidates.  XT: the rules hold text rules (ximg, k_excl_text's image).  GI: both images read in place
+// (they do not fit LDS together); else img, then ximg from the next 16-byte boundary.
+template <bool GI, bool XT>
+__global__ __launch_bounds__(256) void k_win_lik(const RulesDev R, const uint4* __restrict__ img, const LdsImage li,
+                                                 const uint4* __restrict__ ximg, const LdsImage xli, const WinRing W,
+                                                 const WinBatch B, const int16_t* __restrict__ win_ctx,
+                                                 const uint64_t* __restrict__ fbase, uint64_t fcap,
+                                                 uint8_t* __restrict__ wlik, const uint32_t* __restrict__ err) {
+    extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
+    if (*err & (ERR_ABORT | ERR_SLOT)) return;
+    if (fbase[B.n_utt] > fcap) return;            // findings arena (and wlik) too small: k_win_select reports it
+    const uint8_t* lb = load_image<GI>(img, li.total, lds4);
+    const WinLikTabs L{Pool{reinterpret_cast<const uint16_t*>(lb + li.off[WS_TRANS]), lb + li.off[WS_CMAP]},
+                       reinterpret_cast<const int32_t*>(lb + li.off[WS_HDESC]),
+                       reinterpret_cast<const int32_t*>(lb + li.off[WS_HRULE]),
+                       lb + li.off[WS_DLIK],
+                       lb + li.off[WS_ROFF],
+                       li.aux & 7u,
+                       reinterpret_cast<const uint32_t*>(lb + li.off[WS_RLOFF]),
+                       reinterpret_cast<const uint16_t*>(lb + li.off[WS_RIDS])};
+    const uint16_t* dtype = reinterpret_cast<const uint16_t*>(lb + li.off[WS_DTYPE]);
+    const uint8_t* ven = lb + li.off[WS_VEN];
+    const uint8_t* vmin = lb + li.off[WS_VMIN];
+    TextExclTabs X{};
+    if (XT) {
+        const uint8_t* xb = load_image<GI>(ximg, xli.total, lds4 + (GI ? 0u : (li.total + 15u) / 16u));
+        X.pool = Pool{reinterpret_cast<const uint16_t*>(xb + xli.off[TX_TRANS]), xb + xli.off[TX_CMAP]};
+        X.desc = reinterpret_cast<const int32_t*>(xb + xli.off[TX_DESC]);
+        X.rule = reinterpret_cast<const int32_t*>(xb + xli.off[TX_RULE]);
+        X.dtype = dtype;
+        X.ix = xb + xli.off[TX_OFF];
+        X.w = xli.aux & 7u;
+        X.loff = reinterpret_cast<const uint32_t*>(xb + xli.off[TX_LOFF]);
+        X.ids = reinterpret_cast<const uint16_t*>(xb + xli.off[TX_IDS]);
+    }
+    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t u = (uint32_t)(gid / W.N);
+    const int j = (int)(gid % W.N);
+    if (u >= B.n_utt) return;
+    const WinIt it = win_begin(W, B, u);
+    const int nw = it.nw;
+    if (j >= nw) return;
+    uint32_t WL = 0, oj = 0, cb = 0;              // window length, entry j's offset, its first candidate's index
+    for (int i = 0; i < nw; ++i) {
+        const WEntry Ei = win_at(W, B, it, i);
+        if (i < j) {
+            oj += Ei.len + 1;
+            cb += Ei.nc;
+        }
+        WL += Ei.len + 1;
+    }
+    WL -= 1;
+    const WEntry Ej = win_at(W, B, it, j);
+    const int T = R.T;
+    const int g = win_ctx[u];
+    const int v = g >= 0 ? g + 1 : 0;
+    const int minlik = vmin[v];
+    uint8_t* wl = wlik + fbase[u] + cb;
+    for (uint32_t k = 0; k < Ej.nc; ++k) {
+        const WCand C = Ej.c[k];
+        uint8_t b = WLIK_LIK;
+        if (!C.ext) {
+            const uint32_t key = (uint32_t)(v * T) + dtype[C.p];
+            if (ven[key]) {
+                const int lik = win_cand_lik(L, W, B, it, C, (int)C.s, (int)C.e, j, nw, oj, Ej.len, WL, key);
+                if (lik >= minlik) {
+                    b = (uint8_t)lik;
+                    if (XT) {
+                        uint32_t r0, r1;
+                        list_range<true>(X.ix, X.w, X.loff, key, r0, r1);
+                        for (uint32_t q = r0; q < r1 && !(b & WLIK_TEXT); ++q) {
+                            const uint32_t h = X.ids[q];
+                            const int kind = X.rule[4 * h];
+                            const int32_t* d = X.desc + 8 * h;
+                            bool acc;
+                            if (kind == XT_HOTWORD) {
+                                const uint32_t wb = (uint32_t)X.rule[4 * h + 1], wa = (uint32_t)X.rule[4 * h + 2];
+                                const uint32_t ps = oj + C.s, pe = oj + C.e;
+                                acc = wb > 0 && hot_run_win(X.pool, d, W, B, it, ps > wb ? ps - wb : 0u, ps);
+                                if (!acc && wa > 0) acc = hot_run_win(X.pool, d, W, B, it, pe, wa < WL - pe ? pe + wa : WL);
+                            } else {
+                                acc = hot_run_pre(X.pool, d, Ej.t, (int)C.s, (int)C.e);
+                            }
+                            if (acc != (kind == XT_INVERSE)) b |= WLIK_TEXT;
+                        }
+                    }
+                }
+            }
+        }
+        wl[k] = b;
+    }
+}
+
+// k_win_xmark (launched only when the rules hold an exclude_info_types list): one thread per window
+// candidate, ci < fbase[n_utt].  Its window is the last u with fbase[u] <= ci (binary search, as k_win_mask
+// finds its window), its entry the one its running index falls in.  A candidate whose (v, type) list is not
+// empty scans its entry's candidates, start-sorted, up to the first g.s >= c.e, for an excluding
+// occurrence: at most the entry's candidates, slot_bytes / 16 of a ring entry.  It reads the others'
+// likelihood bits only and sets WLIK_TYPE in its own byte only.
+__global__ __launch_bounds__(256) void k_win_xmark(const ExclTabs X, const WinRing W, const WinBatch B,
+                                                   const int16_t* __restrict__ win_ctx,
+                                                   const uint64_t* __restrict__ fbase, uint64_t fcap,
+                                                   uint8_t* __restrict__ wlik, const uint32_t* __restrict__ err) {
+    if (*err & (ERR_ABORT | ERR_SLOT)) return;
+    const uint64_t total = fbase[B.n_utt];
+    if (total > fcap) return;
+    const uint64_t ci = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ci >= total) return;
+    const uint8_t own = wlik[ci];
+    if ((own & WLIK_LIK) == WLIK_LIK) return;
+    uint32_t lo = 0, hi = B.n_utt - 1;                  // last window whose first candidate is at or before ci
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (fbase[mid] <= ci) lo = mid;
+        else hi = mid - 1;
+    }
+    const uint32_t u = lo;
+    const WinIt it = win_begin(W, B, u);
+    uint32_t k = (uint32_t)(ci - fbase[u]);
+    WEntry E = win_at(W, B, it, 0);
+    for (int j = 0; k >= E.nc && j + 1 < it.nw;) {
+        k -= E.nc;
+        E = win_at(W, B, it, ++j);
+    }
+    if (k >= E.nc) return;
+    const WCand C = E.c[k];
+    if (C.ext) return;
+    const int g = win_ctx[u];
+    const uint32_t key = (uint32_t)(g >= 0 ? g + 1 : 0) * (uint32_t)X.T + X.dtype[C.p];
+    const uint32_t q0 = X.xoff[key], q1 = X.xoff[key + 1];
+    if (q0 == q1) return;
+    const uint8_t* wl = wlik + (ci - k);                // the entry's bytes
+    bool hit = false;
+    for (uint32_t i = 0; i < E.nc && !hit; ++i) {
+        const WCand G = E.c[i];
+        if (G.s >= C.e) break;
+        if (i == k || G.ext || G.e <= C.s || (wl[i] & WLIK_LIK) == WLIK_LIK) continue;
+        const uint32_t tg = X.dtype[G.p];
+        for (uint32_t q = q0; q < q1; ++q) {
+            const uint32_t id = X.xids[q];
+            if ((id & (XG_PARTIAL - 1u)) == tg && ((id & XG_PARTIAL) || (G.s <= C.s && C.e <= G.e))) hit = true;
+        }
+    }
+    if (hit) wlik[ci] = own | WLIK_TYPE;
+}
+
 // per window: the window's context variant -> hotword likelihoods (resident bits, or a re-run over
 // the halo when a proximity window crosses a '\n'), min likelihood, exclusion, overlap; findings in
 // window coordinates, output length
 // XR: as in k_win_halo; an external record competes like select_run's ext_cand: its type enabled in the
 // variant, min likelihood, overlap resolution -- no hotword rule, no exclusion on either side
-template <bool GI, bool XR = false>
+// XG: each candidate's likelihood and drop marks come from wlik (k_win_lik, k_win_xmark); a dropped one is
+// one below min_likelihood (the streaming lists of such rules are empty, no pattern has an excluder slot)
+template <bool GI, bool XR = false, bool XG = false>
 __global__ __launch_bounds__(256) void k_win_select(const RulesDev R, const uint4* __restrict__ img, const LdsImage li,
                                                     const WinRing W, const WinBatch B,
                                                     const int16_t* __restrict__ win_ctx,
                                                     const uint64_t* __restrict__ fbase, uint64_t fcap,
                                                     pii_span* __restrict__ wfd, uint32_t* __restrict__ n_wfind,
-                                                    uint32_t* __restrict__ wout_len, uint32_t* __restrict__ err) {
+                                                    uint32_t* __restrict__ wout_len, uint32_t* __restrict__ err,
+                                                    const uint8_t* __restrict__ wlik = nullptr) {
     extern __shared__ __attribute__((aligned(16))) uint4 lds4[];
     if (*err & (ERR_ABORT | ERR_SLOT)) return;
     const uint8_t* lb = load_image<GI>(img, li.total, lds4);
@@ -4283,6 +4493,8 @@ __global__ __launch_bounds__(256) void k_win_select(const RulesDev R, const uint
         if (u == 0) atomicOr(err, (uint32_t)ERR_QUEUE);
         return;
     }
+    const uint8_t* wl = XG ? wlik + fbase[u] : nullptr;
+    uint32_t ci = 0;                              // (XG) the entry's first candidate's index in the window
     const WinIt it = win_begin(W, B, u);
     const int nw = it.nw;
     uint32_t WL = 0;
@@ -4332,7 +4544,15 @@ __global__ __launch_bounds__(256) void k_win_select(const RulesDev R, const uint
                 continue;
             }
             const int t = dtype[p];
+            if (XG) {                                 // (k_win_lik tested ven and min likelihood)
+                const uint8_t b = wl[ci + k];
+                if ((b & WLIK_LIK) != WLIK_LIK && !(b & (WLIK_TYPE | WLIK_TEXT)))
+                    K.consider<true>(X, (uint32_t)(v * T + t), s, e, t, (int)b, 0xff);
+                continue;
+            }
             if (!ven[v * T + t]) continue;
+            // (win_cand_lik, written out: as a call the instantiations without XG land at 80 VGPRs and 6 waves/SIMD,
+            // not the 81 and 5 their timings were taken at, like record_excluder below)
             int lik = dlik[p];
             uint32_t r0, r1;
             list_range<true>(rix, li.aux & 7u, rloff, (uint32_t)(v * T + t), r0, r1);
@@ -4374,6 +4594,7 @@ __global__ __launch_bounds__(256) void k_win_select(const RulesDev R, const uint
         }
         flush_start();
         oj += Ej.len + 1;
+        if (XG) ci += Ej.nc;
     }
     n_wfind[u] = nf;
     wout_len[u] = (uint32_t)((int)WL + delta);
@@ -5019,6 +5240,11 @@ struct pii_engine {
     // findings' output positions (k_win_pos), indexed like wfd
     uint32_t* wpos = nullptr;
     uint64_t wpos_cap = 0;
+    // ... of an engine enabled with PII_WINDOW_XG whose rules are PII_EXCLUSION_GENERAL (win_xg): one byte
+    // per window candidate (k_win_lik, k_win_xmark), indexed like wfd
+    bool window_xg_ok = false, win_xg = false;
+    uint8_t* wlik = nullptr;
+    uint64_t wlik_cap = 0;
     // external candidates on the window paths (pii_rescan_window_ext): set by the first such call, from then
     // on the rings may hold external records and the XR kernels run; the rows' merged lists (k_win_ext)
     bool win_ext = false;
@@ -5740,11 +5966,19 @@ int run_pipeline(pii_engine* e, const Call& c, const WinFull* wf = nullptr) {
     return end_call(e, c.st, hist_bytes(e), true);
 }
 
+// k_win_lik's dynamic LDS: k_win_select's image and, after it, the text rules' -- 0 = read in place (one of
+// them is past LDS, or both do not fit it together)
+size_t win_lik_lds(const pii_engine* e) {
+    const size_t a = ((size_t)e->img_wsel.li.total + 15) / 16 * 16, b = e->excl_text ? e->img_xtext.li.total : 0;
+    return e->img_wsel.global || (e->excl_text && e->img_xtext.global) || a + b > IMG_LDS_MAX ? 0 : a + b;
+}
+
 // the incremental path runs k_win_mask / k_win_hash (only an engine enabled with PII_WINDOW_XF gets here
 // with such rules: any other takes the full re-scan)
 bool win_xpos(const pii_engine* e) { return !e->win_full && (e->xf_mask || e->xf_hash); }
 
-// the window findings arena holds at least `want` records; with win_xpos, so does the position array
+// the window findings arena holds at least `want` records; with win_xpos, so does the position array, with
+// win_xg the candidate bytes
 int ensure_window_findings(pii_engine* e, uint64_t want) {
     int rc;
     if (e->wfd_cap < want) {
@@ -5754,6 +5988,10 @@ int ensure_window_findings(pii_engine* e, uint64_t want) {
     if (win_xpos(e) && e->wpos_cap < e->wfd_cap) {
         if ((rc = grow(e, e->wpos, e->wfd_cap))) return rc;
         e->wpos_cap = e->wfd_cap;
+    }
+    if (e->win_xg && e->wlik_cap < e->wfd_cap) {
+        if ((rc = grow(e, e->wlik, e->wfd_cap))) return rc;
+        e->wlik_cap = e->wfd_cap;
     }
     return PII_OK;
 }
@@ -5978,10 +6216,27 @@ int run_window(pii_engine* e, const Call& c) {
     if (c.n_utt > 0) {
         k_win_plan<<<nb, 256, 0, c.st>>>(W, B, e->wbound, e->wnew, e->d_err);
         if ((rc = exclusive_scan(e, e->wbound, c.n_utt, e->wfbase, c.st))) return rc;
-        (xr ? (e->img_wsel.global ? k_win_select<true, true> : k_win_select<false, true>)
-            : (e->img_wsel.global ? k_win_select<true> : k_win_select<false>))<<<nb, 256, e->img_wsel.lds(), c.st>>>(
-            R, e->img_wsel.d, e->img_wsel.li, W, B, wctx, e->wfbase,
-                                                             e->wfd_cap, e->wfd, e->n_wfind, e->wout_len, e->d_err);
+        if (e->win_xg) {    // the exclusions of each window over its resident candidates: wlik, then the selection reads it
+            const size_t ll = win_lik_lds(e);
+            const uint32_t nlb = (uint32_t)(((uint64_t)c.n_utt * e->win_n + 255) / 256);
+            (e->excl_text ? (ll ? k_win_lik<false, true> : k_win_lik<true, true>)
+                          : (ll ? k_win_lik<false, false> : k_win_lik<true, false>))<<<nlb, 256, ll, c.st>>>(
+                R, e->img_wsel.d, e->img_wsel.li, e->img_xtext.d, e->img_xtext.li, W, B, wctx, e->wfbase, e->wfd_cap, e->wlik,
+                e->d_err);
+            // (the host does not know the candidate count: no more than the arena)
+            if (e->excl_lists)
+                k_win_xmark<<<(uint32_t)(e->wfd_cap / 256) + 1, 256, 0, c.st>>>(e->xt, W, B, wctx, e->wfbase, e->wfd_cap,
+                                                                               e->wlik, e->d_err);
+            (xr ? (e->img_wsel.global ? k_win_select<true, true, true> : k_win_select<false, true, true>)
+                : (e->img_wsel.global ? k_win_select<true, false, true> : k_win_select<false, false, true>))<<<
+                nb, 256, e->img_wsel.lds(), c.st>>>(R, e->img_wsel.d, e->img_wsel.li, W, B, wctx, e->wfbase, e->wfd_cap, e->wfd,
+                                                    e->n_wfind, e->wout_len, e->d_err, e->wlik);
+        } else {
+            (xr ? (e->img_wsel.global ? k_win_select<true, true> : k_win_select<false, true>)
+                : (e->img_wsel.global ? k_win_select<true> : k_win_select<false>))<<<nb, 256, e->img_wsel.lds(), c.st>>>(
+                R, e->img_wsel.d, e->img_wsel.li, W, B, wctx, e->wfbase, e->wfd_cap, e->wfd, e->n_wfind, e->wout_len, e->d_err,
+                nullptr);
+        }
         HIPCHK(hipGetLastError());
     }
     if (c.n_utt > 0) {
@@ -6218,6 +6473,7 @@ bool upload_rules(pii_engine* e, HostRules& H) {
     e->xf_mask = H.xf_mask;
     e->xf_hash = H.xf_hash;
     e->window_ok = H.window_ok;
+    e->window_xg_ok = H.window_xg_ok && H.excl_general;
     return true;
 }
 
@@ -6244,12 +6500,17 @@ bool raise_lds_limits(pii_engine* e) {
         {(const void*)k_pair_eval<false, false, true>, &e->img_eval},
         {(const void*)k_win_eval<false>, &e->img_eval},
         {(const void*)k_win_select<false>, &e->img_wsel}, {(const void*)k_win_select<false, true>, &e->img_wsel},
+        {(const void*)k_win_select<false, false, true>, &e->img_wsel},
+        {(const void*)k_win_select<false, true, true>, &e->img_wsel},
+        {(const void*)k_win_lik<false, false>, &e->img_wsel},
         {(const void*)k_excl_text<false>, &e->img_xtext}};
     // k_win_halo<false>: its image plus HALO_LDS of tables (the launch falls back to <true> past the LDS)
     if (!raise((const void*)k_win_halo<false>, IMG_LDS_MAX) || !raise((const void*)k_win_halo<false, true>, IMG_LDS_MAX))
         return false;
     for (auto& kb : big)
         if (!kb.second->global && !raise(kb.first, kb.second->li.total)) return false;
+    // k_win_lik<false, true>: both images (the launch falls back to <true, true> past the LDS)
+    if (e->excl_text && win_lik_lds(e) && !raise((const void*)k_win_lik<false, true>, win_lik_lds(e))) return false;
     const size_t max_lds = e->max_sg_lds;
     return raise((const void*)k_scan<true>, max_lds) && raise((const void*)k_scan<false>, max_lds) &&
            raise((const void*)k_scan<false, SCAN_BLOCK_WIDE>, max_lds) && raise((const void*)k_scan_fix, max_lds + FIX_LDS);
@@ -6430,8 +6691,9 @@ int pii_reserve(pii_engine* e, uint32_t max_utt, uint64_t max_bytes, uint64_t ma
     if ((rc = ensure_scratch(e, max_utt, max_bytes, (uint32_t)std::min<uint64_t>(lanes, 0xffffffffull))) ||
         (rc = ensure_queues(e, max_bytes)) || (rc = ensure_redact(e, max_spans, max_out)))
         return rc;
-    // (the window calls of an engine with the position array: the per-row arrays and the findings arena too)
-    if (e->win_n && win_xpos(e) &&
+    // (the window calls of an engine with the position array or the candidate bytes: the per-row arrays and
+    // the findings arena too)
+    if (e->win_n && (win_xpos(e) || e->win_xg) &&
         ((rc = ensure_window_scratch(e, max_utt)) || (rc = ensure_window_findings(e, max_spans))))
         return rc;
     if (e->lb_cap < LB_MAX_TILES + 64) {      // the look-back scans' tile states (exclusive_scan: two scans)
@@ -6744,7 +7006,7 @@ int pii_scan_redact_device_ext(pii_engine* e, const uint8_t* d_bytes, const uint
 
 int pii_window_enable_ex(pii_engine* e, uint32_t window_n, uint32_t slot_bytes, uint32_t flags) {
     if (!e || window_n == 0 || window_n > WN_MAX || slot_bytes < 64 || slot_bytes % 16 ||
-        (flags & ~(uint32_t)(PII_WINDOW_FULL | PII_WINDOW_XF)))
+        (flags & ~(uint32_t)(PII_WINDOW_FULL | PII_WINDOW_XF | PII_WINDOW_XG)))
         return PII_E_ARG;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -6766,7 +7028,11 @@ int pii_window_enable_ex(pii_engine* e, uint32_t window_n, uint32_t slot_bytes, 
     // pipeline the full re-scan runs produces both; with PII_WINDOW_XF the incremental path does, by
     // k_win_redact<WT, true>, k_win_mask and k_win_hash)
     const bool xf_full = !(flags & PII_WINDOW_XF) && (e->xf_src || e->xf_hash);
-    e->win_full = (flags & PII_WINDOW_FULL) || !e->window_ok || xf_full;
+    // (general / text exclusion rules, and nothing else, took window_ok: with PII_WINDOW_XG the windows decide
+    // them over their resident candidates, by k_win_lik, k_win_xmark and k_win_select<GI, XR, true>)
+    const bool xg = (flags & PII_WINDOW_XG) && e->window_xg_ok;
+    e->win_full = (flags & PII_WINDOW_FULL) || xf_full || !(e->window_ok || xg);
+    e->win_xg = !e->win_full && !e->window_ok;
     e->win_n = window_n;
     e->win_slot_bytes = slot_bytes;
     e->win_ext = false;                  // (fresh rings)

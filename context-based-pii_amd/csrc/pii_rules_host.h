@@ -329,6 +329,7 @@ struct HostRules {
     std::vector<uint8_t> xf_kind;
     bool xf_src = false, xf_mask = false, xf_hash = false;
     bool window_ok = false;
+    bool window_xg_ok = false;         // general / text exclusion rules alone took window_ok (meta[15]; absent: no)
     // general exclusion rules (var.xg_off / var.xg_ids / det.xgidx): k_exclude decides them, the
     // streaming lists are empty; excl_nx = its excluder patterns
     bool excl_general = false;
@@ -443,6 +444,7 @@ inline bool read_core(const Blob& B, CoreSecs& c, HostRules& H) {
     }
     R.min_len = (int)std::clamp<int64_t>(c.meta[11], 1, 1 << 30);
     H.window_ok = c.meta[13] != 0;
+    H.window_xg_ok = !H.window_ok && c.meta.n > 15 && c.meta[15] != 0;
     if (R.P > 65535) return bad("too many detector patterns");
     // scan table entries are 16-bit LDS byte addresses (k_scan layout: class map, D rows, K rows);
     // rows are padded to an even class count so every row address is a multiple of 4 and bit 1 of

@@ -32,6 +32,7 @@ EXPORTS = ["pii_engine_create", "pii_engine_destroy", "pii_engine_info", "pii_ty
            "pii_rescan_window_ext", "pii_rescan_window_device_ext"]
 PII_WINDOW_FULL = 1
 PII_WINDOW_XF = 2
+PII_WINDOW_XG = 16    # (4 and 8 are not flags: pii_window_enable_ex answers PII_E_ARG)
 # pii_type_transform: what the rules' deidentify_config does with a finding of a type
 PII_XF_INFO_TYPE, PII_XF_REPLACE, PII_XF_REDACT, PII_XF_MASK, PII_XF_KEEP, PII_XF_HASH = range(6)
 
@@ -248,12 +249,14 @@ class Engine:
         return self._host_call(fn, "pii_rescan_window_ext", texts, conv_slot, role, ts_us, n)
 
     def window_enable(self, window_n: int = 5, slot_bytes: int = 8192, full: bool = False,
-                      incremental_transforms: bool = False) -> None:
+                      incremental_transforms: bool = False, incremental_exclusions: bool = False) -> None:
         """full=True forces the full re-scan of the joined windows (rule sets the incremental path
         cannot take get it anyway: window_mode() tells which one runs).  incremental_transforms=True
         (PII_WINDOW_XF): a character_mask_config, kept or crypto_hash_config type no longer forces the full
-        re-scan; the output is the same."""
-        flags = (PII_WINDOW_FULL if full else 0) | (PII_WINDOW_XF if incremental_transforms else 0)
+        re-scan; incremental_exclusions=True (PII_WINDOW_XG): nor do general or text exclusion rules
+        (exclusion_mode() == 1); the output is the same."""
+        flags = ((PII_WINDOW_FULL if full else 0) | (PII_WINDOW_XF if incremental_transforms else 0) |
+                 (PII_WINDOW_XG if incremental_exclusions else 0))
         rc = self.lib.pii_window_enable_ex(self.h, window_n, slot_bytes, flags)
         if rc != PII_OK:
             raise self._err(rc, "pii_window_enable_ex")

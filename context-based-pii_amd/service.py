@@ -609,17 +609,21 @@ class PiiService:
 
     # ---------------------------------------------------------------- aggregator re-scan (a12)
     def rescan_window_batch(self, rows: Sequence[dict], window_n: int = 5, slot_bytes: int = 8192,
-                            incremental_transforms: bool = False) -> List[str]:
+                            incremental_transforms: bool = False,
+                            incremental_exclusions: bool = False) -> List[str]:
         """Rows as process_batch (original text) -> per row the redacted window
         "\\n".join(last window_n utterances of its conversation), re-scanned with the conversation's
         current expected_pii_type.  Agent rows update the context as handle_agent_utterance does.
-        incremental_transforms: the call that enables the window passes it on (Engine.window_enable)."""
+        incremental_transforms, incremental_exclusions: the call that enables the window passes them on
+        (Engine.window_enable)."""
         with self.lock:
             if getattr(self.engine, "window_n", 0) == 0:
+                kw = {}
                 if incremental_transforms:
-                    self.engine.window_enable(window_n, slot_bytes, incremental_transforms=True)
-                else:
-                    self.engine.window_enable(window_n, slot_bytes)
+                    kw["incremental_transforms"] = True
+                if incremental_exclusions:
+                    kw["incremental_exclusions"] = True
+                self.engine.window_enable(window_n, slot_bytes, **kw)
             elif self.engine.window_n != window_n:
                 raise ValueError(f"window already enabled with N={self.engine.window_n}")
         out: List[str] = []

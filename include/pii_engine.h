@@ -271,8 +271,9 @@ int pii_last_stats(struct pii_engine* e, uint64_t* out, uint32_t n);
  * rules hold an exclude_info_types list), then runs the text rules' automata over each remaining
  * candidate of a type that has one and marks those they drop.  Rows cut into lanes are exact (a cut row's
  * occurrences are gathered by one thread, serially; the text rules read row positions).  Such rules
- * re-scan windows by the FULL path (pii_window_mode): over the joined window a hotword window reaches
- * across the "\n" joins.  The occurrence list is a work buffer sized by the batch bytes (pii_reserve covers
+ * re-scan windows by the FULL path (pii_window_mode) unless the window is enabled with PII_WINDOW_XG (see
+ * the window re-scan below): over the joined window a hotword window reaches across the "\n" joins, on
+ * either path.  The occurrence list is a work buffer sized by the batch bytes (pii_reserve covers
  * it); an overflow is re-run by pii_sync like the other queues.  Refused by the rule compiler:
  * exclude_info_types with INVERSE_MATCH, regex / hotword_regex group_indexes, dictionary
  * cloud_storage_path, patterns that match the empty string, and rules naming an external type. */
@@ -295,22 +296,36 @@ int pii_exclusion_mode(struct pii_engine* e);
  * re-scan -- the ring then keeps the raw text, every row's "\n"-joined window is materialised in HBM
  * and run through the scan+redact pipeline (one host wait per call for the joined size).  Rules with a
  * PII_XF_MASK, PII_XF_KEEP or PII_XF_HASH type (output bytes taken or computed from the text) also
- * take the FULL re-scan, unless the window is enabled with PII_WINDOW_XF: then
- *     full = (flags & PII_WINDOW_FULL) || the rules are not incremental ('\n'-consuming detector, general
- *            or text exclusion rules)
- * and such rules run incrementally too: a mask / keep finding's bytes are copied from its resident entry,
- * then one thread per window finding masks its code points or computes its surrogate over the placeholder
- * (a surrogate is computed again in every window that holds the finding).  Same bytes, spans and offsets as
- * the FULL re-scan; without the flag nothing changes. */
+ * take the FULL re-scan, unless the window is enabled with PII_WINDOW_XF; so do rules of
+ * PII_EXCLUSION_GENERAL (general or text exclusion rules), unless it is enabled with PII_WINDOW_XG:
+ *     full = (flags & PII_WINDOW_FULL)
+ *            || (a mask / keep / hash type && !(flags & PII_WINDOW_XF))
+ *            || a detector consumes '\n' or tests a text edge
+ *            || (general or text exclusion rules && !(flags & PII_WINDOW_XG))
+ * With PII_WINDOW_XF a mask / keep finding's bytes are copied from its resident entry, then one thread per
+ * window finding masks its code points or computes its surrogate over the placeholder (a surrogate is
+ * computed again in every window that holds the finding).  With PII_WINDOW_XG each window decides the
+ * exclusions again over its resident candidates: an excluder occurrence is itself a resident candidate of
+ * the same utterance, so per window candidate one byte of work buffer (likelihood under the window's
+ * variant, text-rule mark, type-rule mark; it counts against pii_set_scratch_limit and pii_reserve covers
+ * it) is written by a likelihood pass (which also runs the text rules' automata: over the candidate's own
+ * bytes, or for exclude_by_hotword over the joined window, across the "\n" joins) and a marking pass (one
+ * thread per window candidate scans its utterance's candidates for an excluding occurrence: at most
+ * slot_bytes / 16 of them); selection then reads the byte.  A text rule's result is not kept in the ring:
+ * it is computed again in every window.  The flags combine.  Same bytes, spans and offsets as the FULL
+ * re-scan; without a flag nothing changes, and PII_WINDOW_XG has no effect on rules of
+ * PII_EXCLUSION_STREAMING or on a blob compiled before the flag existed (FULL). */
 #define PII_WINDOW_MAX 8
 #define PII_WINDOW_FULL 1   /* pii_window_enable_ex flag / pii_window_mode result: full re-scan */
 #define PII_WINDOW_XF 2     /* pii_window_enable_ex flag: mask / keep / hash types do not force the full re-scan */
+#define PII_WINDOW_XG 16    /* pii_window_enable_ex flag: general / text exclusion rules do not force the full re-scan
+                             * (bits 4 and 8 are not flags: PII_E_ARG, as they have always been) */
 /* allocate the per-slot window history (n_conv_slots * slot_bytes of HBM); window_n <= PII_WINDOW_MAX,
  * slot_bytes a multiple of 16 (a window must fit: its utterances, each rounded up to 16 B, + 16 B per
  * resident candidate, external ones (pii_rescan_window_ext) included) */
 int pii_window_enable(struct pii_engine* e, uint32_t window_n, uint32_t slot_bytes);
 /* the same; flags: PII_WINDOW_FULL forces the full re-scan even for rules the incremental path takes (with
- * or without PII_WINDOW_XF), PII_WINDOW_XF see above; any other bit is PII_E_ARG */
+ * or without the other flags), PII_WINDOW_XF and PII_WINDOW_XG see above; any other bit is PII_E_ARG */
 int pii_window_enable_ex(struct pii_engine* e, uint32_t window_n, uint32_t slot_bytes, uint32_t flags);
 /* PII_WINDOW_FULL or 0 (incremental) for an enabled window, else PII_E_ARG */
 int pii_window_mode(struct pii_engine* e);
