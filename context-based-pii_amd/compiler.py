@@ -811,14 +811,19 @@ def minimize(dfa: DFA) -> DFA:
 # What happens to a finding's bytes (dlp_config.yaml:195-199): per info type, the first transformation
 # that lists it, else the first without info_types, else the bytes stay (DLP leaves findings no
 # transformation names).  The values are the engine's PII_XF_* (include/pii_engine.h).
-XF_INFO_TYPE, XF_REPLACE, XF_REDACT, XF_MASK, XF_KEEP, XF_HASH = range(6)
+XF_INFO_TYPE, XF_REPLACE, XF_REDACT, XF_MASK, XF_KEEP, XF_HASH, XF_FPE = range(7)
 XF_MASK_WORDS = 8          # per type: char | reverse << 8, number_to_mask, 4 words of skip set, 2 spare
 XF_REPLACE_MAX = 255
 XF_HASH_LEN = 44           # base64 of a SHA-256 digest
 XF_HASH_KEY_WORDS = 16     # per key: the inner, then the outer HMAC midstate (8 words each)
+XF_FPE_KEY_WORDS = 64      # per key: Nr, the 4 * (Nr + 1) <= 60 AES round-key words, zeros
+XF_FPE_ALPHA_WORDS = 68    # per alphabet: radix, nmin, nmax, 0; byte -> digit [128]; digit -> byte [96]; b(v) [32]
+XF_FPE_NMAX = 64           # numerals the engine encrypts at most (v <= 32: b(v) has 32 entries)
+XF_FPE_KEYS_MAX = 16       # distinct FPE keys in one config (the kernels hold the round keys in LDS)
 _XF_PRIMITIVES = {"replace_with_info_type_config": XF_INFO_TYPE, "replace_config": XF_REPLACE,
                   "redact_config": XF_REDACT, "character_mask_config": XF_MASK, "crypto_hash_config": XF_HASH}
 # every other primitive of DLP's PrimitiveTransformation: named in the error when one is configured
+# (crypto_replace_ffx_fpe_config: refused only without fpe=True, see _parse_primitive)
 _XF_UNSUPPORTED = ("crypto_replace_ffx_fpe_config", "crypto_deterministic_config",
                    "date_shift_config", "bucketing_config", "fixed_size_bucketing_config", "time_part_config",
                    "replace_dictionary_config")
@@ -835,7 +840,8 @@ class Transform:
     count: int = 0             # 0 = every character
     reverse: bool = False
     skip: int = 0              # 128-bit ASCII set: copied and not counted
-    key: bytes = b""           # XF_HASH: the HMAC-SHA256 key (32 or 64 bytes)
+    key: bytes = b""           # XF_HASH: the HMAC-SHA256 key (32 or 64 bytes); XF_FPE: the AES key (16, 24, 32)
+    alphabet: str = ""         # XF_FPE: the numerals' characters, a numeral's value = its position
 
 
 def _parse_mask(cfg: dict) -> Transform:
@@ -944,11 +950,153 @@ def _parse_hash(cfg: dict) -> Transform:
     return Transform(XF_HASH, key=key)
 
 
-def _parse_primitive(prim: dict) -> Transform:
+# crypto_replace_ffx_fpe_config: a finding's characters of the alphabet are encrypted among themselves with
+# FF1 (NIST SP 800-38G) over AES under an empty tweak; every other byte stays.  The blob carries
+# the AES round keys (FIPS-197 5.2), expanded here, and per alphabet the two character maps, the limits on
+# the numeral count and b(v), the byte length of radix^v - 1, which FF1 defines through a logarithm.
+_FPE_NAME = "crypto_replace_ffx_fpe_config"
+_FPE_COMMON = {"NUMERIC": "0123456789", "HEXADECIMAL": "0123456789ABCDEF",
+               "UPPER_CASE_ALPHA_NUMERIC": "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ",
+               "ALPHA_NUMERIC": "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz"}
+
+
+def _aes_sbox() -> List[int]:
+    """FIPS-197 5.1.1: the multiplicative inverse in GF(2^8) (p runs through the powers of 3, q through
+    their inverses), then the affine transformation"""
+    box = [0x63] * 256
+    p = q = 1
+    while True:
+        p = (p ^ (p << 1) ^ (0x1B if p & 0x80 else 0)) & 0xFF
+        q ^= q << 1
+        q ^= q << 2
+        q ^= q << 4
+        q &= 0xFF
+        if q & 0x80:
+            q ^= 0x09
+        x = q
+        for k in range(1, 5):
+            x ^= ((q << k) | (q >> (8 - k))) & 0xFF
+        box[p] = x ^ 0x63
+        if p == 1:
+            return box
+
+
+_AES_SBOX = _aes_sbox()
+
+
+def aes_round_keys(key: bytes) -> Tuple[int, ...]:
+    """the key schedule w[0 .. 4 * (Nr + 1)) of a 16-, 24- or 32-byte key, big-endian words"""
+    assert len(key) in (16, 24, 32)
+    nk = len(key) // 4
+    w = list(struct.unpack(f">{nk}I", key))
+
+    def sub(x):
+        return int.from_bytes(bytes(_AES_SBOX[b] for b in x.to_bytes(4, "big")), "big")
+    rcon = 1
+    for i in range(nk, 4 * (nk + 7)):
+        t = w[-1]
+        if i % nk == 0:
+            t = sub(((t << 8) | (t >> 24)) & 0xFFFFFFFF) ^ (rcon << 24)
+            rcon = (rcon << 1) ^ (0x11B if rcon & 0x80 else 0)
+        elif nk == 8 and i % nk == 4:
+            t = sub(t)
+        w.append(w[i - nk] ^ t)
+    return tuple(w)
+
+
+def fpe_key_words(key: bytes) -> np.ndarray:
+    """one xf.fpe_key record (XF_FPE_KEY_WORDS words): Nr, the round keys, zeros"""
+    w = aes_round_keys(key)
+    rec = np.zeros(XF_FPE_KEY_WORDS, dtype=np.uint32)
+    rec[0] = len(w) // 4 - 1
+    rec[1:1 + len(w)] = w
+    return rec
+
+
+def fpe_limits(radix: int) -> Tuple[int, int]:
+    """(nmin, nmax) numerals: the least n >= 2 with radix^n >= 100 (SP 800-38G); min(2 * vmax, XF_FPE_NMAX)
+    with radix^vmax <= 2^128, so that NUM(B) fits 16 bytes"""
+    nmin = 2
+    while radix ** nmin < 100:
+        nmin += 1
+    vmax = 1
+    while radix ** (vmax + 1) <= 1 << 128:
+        vmax += 1
+    return nmin, min(2 * vmax, XF_FPE_NMAX)
+
+
+def fpe_alphabet_words(alphabet: str) -> np.ndarray:
+    """one xf.fpe_alpha record (XF_FPE_ALPHA_WORDS words)"""
+    radix = len(alphabet)
+    nmin, nmax = fpe_limits(radix)
+    to_digit = np.full(128, 0xFF, dtype=np.uint8)
+    to_byte = np.zeros(96, dtype=np.uint8)
+    for d, ch in enumerate(alphabet):
+        to_digit[ord(ch)] = d
+        to_byte[d] = ord(ch)
+    # b(v), v = 1 .. 32: the bytes of radix^v - 1; past nmax / 2 it is not used (16 there, so the row stays monotonous)
+    bv = np.array([min(((radix ** v - 1).bit_length() + 7) // 8, 16) for v in range(1, 33)], dtype=np.uint8)
+    rec = np.concatenate([np.array([radix, nmin, nmax, 0], dtype="<u4").view(np.uint8), to_digit, to_byte, bv])
+    assert rec.size == 4 * XF_FPE_ALPHA_WORDS
+    return rec.view("<u4").astype(np.uint32)
+
+
+def _parse_fpe(cfg: dict) -> Transform:
+    cfg = cfg or {}
+    fields = {"crypto_key", "common_alphabet", "custom_alphabet"}
+    for k in ("context", "radix", "surrogate_info_type"):
+        if k in cfg:
+            raise RuleError(f"{_FPE_NAME}: {k} is not supported")
+    unknown = set(cfg) - fields
+    if unknown:
+        raise RuleError(f"{_FPE_NAME}: unsupported field {sorted(unknown)[0]}")
+    ck = cfg.get("crypto_key")
+    if not isinstance(ck, dict) or not ck:
+        raise RuleError(f"{_FPE_NAME}: crypto_key is missing")
+    for k in ck:
+        if k != "unwrapped":
+            known = "unsupported" if k in ("transient", "kms_wrapped") else "unknown"
+            raise RuleError(f"{_FPE_NAME}: {known} crypto_key form {k} (only unwrapped is supported)")
+    uw = ck["unwrapped"]
+    if not isinstance(uw, dict) or "key" not in uw:
+        raise RuleError(f"{_FPE_NAME}: crypto_key.unwrapped.key is missing")
+    unknown = set(uw) - {"key"}
+    if unknown:
+        raise RuleError(f"{_FPE_NAME}: unsupported field unwrapped.{sorted(unknown)[0]}")
+    try:
+        if not isinstance(uw["key"], str):
+            raise ValueError
+        key = base64.b64decode(uw["key"], validate=True)
+    except ValueError:
+        raise RuleError(f"{_FPE_NAME}: crypto_key.unwrapped.key is not base64") from None
+    if len(key) not in (16, 24, 32):
+        raise RuleError(f"{_FPE_NAME}: crypto_key.unwrapped.key is {len(key)} bytes (not 16, 24 or 32)")
+    if ("common_alphabet" in cfg) == ("custom_alphabet" in cfg):
+        raise RuleError(f"{_FPE_NAME}: exactly one of common_alphabet and custom_alphabet is needed")
+    if "common_alphabet" in cfg:
+        name = cfg["common_alphabet"]
+        if not isinstance(name, str) or name not in _FPE_COMMON:
+            raise RuleError(f"{_FPE_NAME}: unknown common_alphabet {name!r}")
+        alphabet = _FPE_COMMON[name]
+    else:
+        alphabet = cfg["custom_alphabet"]
+        if not isinstance(alphabet, str) or not 2 <= len(alphabet) <= 95:
+            raise RuleError(f"{_FPE_NAME}: custom_alphabet does not hold 2 to 95 characters")
+        for ch in alphabet:
+            if not 0x20 <= ord(ch) <= 0x7E:
+                raise RuleError(f"{_FPE_NAME}: custom_alphabet character {ch!r} is not printable ASCII")
+        if len(set(alphabet)) != len(alphabet):
+            raise RuleError(f"{_FPE_NAME}: custom_alphabet repeats a character")
+    return Transform(XF_FPE, key=key, alphabet=alphabet)
+
+
+def _parse_primitive(prim: dict, fpe: bool = False) -> Transform:
     prim = prim or {}
     if len(prim) != 1:
         raise RuleError(f"a primitive_transformation holds exactly one primitive, not {sorted(prim)}")
     (name, cfg), = prim.items()
+    if fpe and name == _FPE_NAME:
+        return _parse_fpe(cfg)
     if name not in _XF_PRIMITIVES:
         known = "unsupported" if name in _XF_UNSUPPORTED else "unknown"
         raise RuleError(f"{known} primitive transformation {name}")
@@ -970,8 +1118,10 @@ def _parse_primitive(prim: dict) -> Transform:
     return Transform(kind)
 
 
-def parse_deidentify(dlp_config: dict, type_names: Sequence[str]) -> List[Transform]:
-    """deidentify_config -> one Transform per info type (type order).  No block: "[TYPE]" for all."""
+def parse_deidentify(dlp_config: dict, type_names: Sequence[str], fpe: bool = False) -> List[Transform]:
+    """deidentify_config -> one Transform per info type (type order).  No block: "[TYPE]" for all.
+    fpe: accept crypto_replace_ffx_fpe_config (_parse_fpe).  Without it the primitive is refused as
+    unsupported, as it always was; compile_default asks for it."""
     if "deidentify_config" not in dlp_config or dlp_config["deidentify_config"] is None:
         return [Transform(XF_INFO_TYPE) for _ in type_names]
     de = dlp_config["deidentify_config"]
@@ -991,7 +1141,7 @@ def parse_deidentify(dlp_config: dict, type_names: Sequence[str]) -> List[Transf
                 raise RuleError(f"transformation: {k} is not supported")
         if "primitive_transformation" not in entry:
             raise RuleError("transformation without a primitive_transformation")
-        tf = _parse_primitive(entry["primitive_transformation"])
+        tf = _parse_primitive(entry["primitive_transformation"], fpe)
         names = [it.get("name") for it in entry.get("info_types", []) or []]
         for n in names:
             if n not in known:
@@ -1038,6 +1188,23 @@ def transform_sections(transforms: Sequence[Transform]) -> "OrderedDict[str, np.
         out["xf.hash_key"] = np.array([keys.index(t.key) if t.kind == XF_HASH else 0 for t in transforms],
                                       dtype=np.uint32)
         out["xf.hash_mid"] = np.array([w for k in keys for mid in hmac_midstates(k) for w in mid], dtype=np.uint32)
+    # crypto_replace_ffx_fpe_config (only with an FPE type): per type key index | alphabet index << 16, per
+    # distinct key its AES round keys, per distinct alphabet its record.  The round keys are as secret as the
+    # key, like the midstates: the raw key follows from them.
+    if any(t.kind == XF_FPE for t in transforms):
+        fkeys: List[bytes] = []
+        alphas: List[str] = []
+        for t in transforms:
+            if t.kind == XF_FPE and t.key not in fkeys:
+                fkeys.append(t.key)
+            if t.kind == XF_FPE and t.alphabet not in alphas:
+                alphas.append(t.alphabet)
+        if len(fkeys) > XF_FPE_KEYS_MAX:
+            raise RuleError(f"{_FPE_NAME}: more than {XF_FPE_KEYS_MAX} distinct keys")
+        out["xf.fpe"] = np.array([fkeys.index(t.key) | alphas.index(t.alphabet) << 16 if t.kind == XF_FPE else 0
+                                  for t in transforms], dtype=np.uint32)
+        out["xf.fpe_key"] = np.concatenate([fpe_key_words(k) for k in fkeys])
+        out["xf.fpe_alpha"] = np.concatenate([fpe_alphabet_words(a) for a in alphas])
     return out
 
 
@@ -1065,7 +1232,7 @@ class HotRule:
 class Rules:
     """The rule model both the engine blob and the docs are generated from."""
 
-    def __init__(self, dlp_config: dict, builtin: dict):
+    def __init__(self, dlp_config: dict, builtin: dict, fpe: bool = False):
         insp = dlp_config.get("inspect_config", {}) or {}
         self.raw = dlp_config
         self.base_info_types = [it.get("name") for it in insp.get("info_types", [])]
@@ -1124,17 +1291,18 @@ class Rules:
             named = {t for t, _, _ in self.kw_groups} | set(self.external_types)
             self.kw_groups.extend((t, None, False) for t in self.type_names if t not in named)
 
-        self.transforms = parse_deidentify(dlp_config, self.type_names)
+        self.transforms = parse_deidentify(dlp_config, self.type_names, fpe)
 
     @classmethod
-    def load(cls, dlp_config_path: Optional[str] = None, builtin_path: Optional[str] = None) -> "Rules":
+    def load(cls, dlp_config_path: Optional[str] = None, builtin_path: Optional[str] = None,
+             fpe: bool = False) -> "Rules":
         dlp_config_path = dlp_config_path or os.path.join(RULES_DIR, "dlp_config.json")
         builtin_path = builtin_path or os.path.join(RULES_DIR, "builtin_infotypes.yaml")
         with open(dlp_config_path) as f:
             cfg = json.load(f) if dlp_config_path.endswith(".json") else yaml.safe_load(f)
         with open(builtin_path) as f:
             builtin = yaml.safe_load(f)
-        return cls(cfg, builtin)
+        return cls(cfg, builtin, fpe)
 
     # ---- a6, main.py:609-686, restated statelessly -------------------------------
     def merged_inspect_config(self, expected_type: Optional[str]) -> dict:
@@ -1744,7 +1912,7 @@ _CACHE: Dict[str, Compiled] = {}
 
 def compile_default(dlp_config_path: Optional[str] = None, builtin_path: Optional[str] = None,
                     cache_dir: Optional[str] = None) -> Compiled:
-    rules = Rules.load(dlp_config_path, builtin_path)
+    rules = Rules.load(dlp_config_path, builtin_path, fpe=True)
     key = hashlib.sha256(json.dumps([rules.raw, [p.__dict__ for p in rules.patterns]], sort_keys=True,
                                     default=str).encode()).hexdigest()[:16]
     if key in _CACHE:

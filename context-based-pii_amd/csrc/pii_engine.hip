@@ -25,6 +25,7 @@
 //                  what the rules' deidentify_config says for its type: out_len), span list, histogram
 //   k_mask         character_mask_config: masks the findings k_redact<true> copied (rules with a mask type)
 //   k_hash         crypto_hash_config: HMAC-SHA256 surrogates over k_redact's placeholders (rules with a hash type)
+//   k_fpe          crypto_replace_ffx_fpe_config: FF1 over the findings k_redact<true> copied (rules with an FPE type)
 //   k_ctx_commit   write the per-conversation context back (only when the call succeeded)
 #include <hip/hip_runtime.h>
 
@@ -38,6 +39,7 @@
 
 #include "../../include/pii_engine.h"
 #include "pii_device.h"
+#include "pii_fpe.h"
 #include "pii_rules_host.h"
 #include "pii_xform.h"
 
@@ -3758,6 +3760,54 @@ __global__ __launch_bounds__(HASH_BLOCK) void k_hash(const uint8_t* __restrict__
              out + rs_out(r));
 }
 
+// crypto_replace_ffx_fpe_config, after k_redact<true> has copied an FPE type's finding to the output
+// unchanged: one thread per span encrypts its characters of the alphabet in place (ff1_apply), so only bytes
+// inside the span's own output range are written.  Launched only for rules with an FPE type; its tables are
+// its own arguments (FpeTabs), RulesDev does not carry them.  A block first copies the AES table and the
+// round keys of every key (nkeys <= XF_FPE_KEYS_MAX, build_host_rules) to LDS; a thread's numerals live there
+// too, numeral i of thread t at s_num[i * FPE_BLOCK + t] (four threads to a bank, each its own byte).
+constexpr int FPE_BLOCK = 128;
+struct FpeTabs {
+    const uint8_t* xf_kind;     // [T]
+    const uint32_t* fpe;        // [T] key | alphabet << 16
+    const uint32_t* key;        // [nkeys * XF_FPE_KEY_WORDS]
+    const uint32_t* alpha;      // [alphabets * XF_FPE_ALPHA_WORDS]
+    const uint32_t* te0;        // [XF_FPE_TE0_WORDS]
+    uint32_t nkeys;
+};
+struct FpeLds {
+    uint32_t te0[XF_FPE_TE0_WORDS];
+    uint32_t key[XF_FPE_KEYS_MAX * XF_FPE_KEY_WORDS];
+    uint8_t num[XF_FPE_NMAX * FPE_BLOCK];
+};
+// (every thread of the block, before any of them leaves)
+__device__ __forceinline__ void fpe_stage(const FpeTabs& F, FpeLds& s) {
+    for (uint32_t i = threadIdx.x; i < (uint32_t)XF_FPE_TE0_WORDS; i += FPE_BLOCK) s.te0[i] = F.te0[i];
+    for (uint32_t i = threadIdx.x; i < F.nkeys * XF_FPE_KEY_WORDS; i += FPE_BLOCK) s.key[i] = F.key[i];
+    __syncthreads();
+}
+__device__ __forceinline__ void fpe_span(const FpeTabs& F, FpeLds& s, uint32_t t, const uint8_t* in, int len,
+                                         uint8_t* o) {
+    const uint32_t ka = F.fpe[t];
+    ff1_apply(s.te0, s.key + (ka & 0xffffu) * XF_FPE_KEY_WORDS, F.alpha + (size_t)(ka >> 16) * XF_FPE_ALPHA_WORDS, in, len, o,
+              s.num + threadIdx.x, FPE_BLOCK);
+}
+__global__ __launch_bounds__(FPE_BLOCK) void k_fpe(const FpeTabs F, const uint8_t* __restrict__ text,
+                                                   const uint64_t* __restrict__ offs, const RSpan* __restrict__ rsp,
+                                                   const uint64_t* __restrict__ n_spans_p,
+                                                   const uint32_t* __restrict__ err, uint8_t* __restrict__ out) {
+    __shared__ FpeLds s;
+    if (*err != 0) return;
+    if ((uint64_t)blockIdx.x * blockDim.x >= *n_spans_p) return;      // (the whole block)
+    fpe_stage(F, s);
+    const uint64_t si = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;      // span index
+    if (si >= *n_spans_p) return;
+    const RSpan r = rsp[si];
+    const uint32_t t = rs_type(r);
+    if (F.xf_kind[t] != PII_XF_FPE) return;
+    fpe_span(F, s, t, text + offs[0] + r.in_lo, (int)(r.in_hi - r.in_lo), out + rs_out(r));
+}
+
 // per-info-type totals of the redact tiles' histograms (one atomic per type, no same-address storms)
 __global__ __launch_bounds__(256) void k_hist_reduce(const uint32_t* __restrict__ hist_part, uint32_t n_tiles, int T,
                                                      const uint32_t* __restrict__ err,
@@ -4892,6 +4942,22 @@ __global__ __launch_bounds__(HASH_BLOCK) void k_win_hash(const uint8_t* __restri
     hmac_b64(hash_mid + (size_t)hash_key[f.t] * XF_HASH_KEY_WORDS, f.in, f.len, f.o);
 }
 
+__global__ __launch_bounds__(FPE_BLOCK) void k_win_fpe(const FpeTabs F, const WinRing W, const WinBatch B,
+                                                       const pii_span* __restrict__ wfd,
+                                                       const uint64_t* __restrict__ fbase,
+                                                       const uint64_t* __restrict__ wspan_offs,
+                                                       const uint32_t* __restrict__ wpos,
+                                                       const uint64_t* __restrict__ out_offs,
+                                                       const uint32_t* __restrict__ err, uint8_t* __restrict__ out) {
+    __shared__ FpeLds s;
+    if (*err != 0) return;
+    if ((uint64_t)blockIdx.x * blockDim.x >= wspan_offs[B.n_utt]) return;      // (the whole block)
+    fpe_stage(F, s);
+    WinFind f;
+    if (!win_find<PII_XF_FPE>(F.xf_kind, W, B, wfd, fbase, wspan_offs, wpos, out_offs, out, f)) return;
+    fpe_span(F, s, f.t, f.in, f.len, f.o);
+}
+
 // after a successful call: the planned rows enter the rings (16 threads per row copy the resident
 // candidates, then the text, as aligned 16-byte stores); descriptors, counts and heads follow
 __global__ __launch_bounds__(256) void k_win_commit(const WinRing W, const WinBatch B, const WNew* __restrict__ wnew,
@@ -5109,9 +5175,11 @@ struct pii_engine {
     uint32_t first_p_hot = 0;
     bool lists_cl = false;
     // deidentify_config (optional xf.* blob sections): per-type PII_XF_*; any mask / keep type (k_redact<true>,
-    // the FULL window re-scan), any mask type (k_mask), any hash type (k_hash, the FULL window re-scan)
+    // the FULL window re-scan), any mask type (k_mask), any hash type (k_hash, the FULL window re-scan), any FPE
+    // type (k_fpe; xf_src covers it)
     std::vector<uint8_t> xf_kind;
-    bool xf_src = false, xf_mask = false, xf_hash = false;
+    bool xf_src = false, xf_mask = false, xf_hash = false, xf_fpe = false;
+    FpeTabs fpe{};                           // (in d_rules) k_fpe's and k_win_fpe's tables
     const uint32_t* d_hash_key = nullptr;    // (in d_rules) per type: key index; per key: its two HMAC midstates
     const uint32_t* d_hash_mid = nullptr;
     hipStream_t aux[2] = {nullptr, nullptr};   // more streams for the SCAN groups' passes (PII_SCAN_STREAMS)
@@ -5949,6 +6017,9 @@ int run_pipeline(pii_engine* e, const Call& c, const WinFull* wf = nullptr) {
             if (e->xf_hash)
                 k_hash<<<(uint32_t)(ms / HASH_BLOCK) + 1, HASH_BLOCK, 0, c.st>>>(
                     R.xf_kind, e->d_hash_key, e->d_hash_mid, c.text, c.offs, e->rsp, e->lane_sp + n_chunks, e->d_err, c.out);
+            if (e->xf_fpe)
+                k_fpe<<<(uint32_t)(ms / FPE_BLOCK) + 1, FPE_BLOCK, 0, c.st>>>(e->fpe, c.text, c.offs, e->rsp,
+                                                                           e->lane_sp + n_chunks, e->d_err, c.out);
             if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->kev[3], c.st));
             if (!wf)        // (window findings are not counted, as on the incremental window path)
                 k_hist_reduce<<<dim3(e->hist_types, std::max(1u, std::min(32u, nsb / 256))), 256, 0, c.st>>>(
@@ -5973,9 +6044,9 @@ size_t win_lik_lds(const pii_engine* e) {
     return e->img_wsel.global || (e->excl_text && e->img_xtext.global) || a + b > IMG_LDS_MAX ? 0 : a + b;
 }
 
-// the incremental path runs k_win_mask / k_win_hash (only an engine enabled with PII_WINDOW_XF gets here
+// the incremental path runs k_win_mask / k_win_hash / k_win_fpe (only an engine enabled with PII_WINDOW_XF gets here
 // with such rules: any other takes the full re-scan)
-bool win_xpos(const pii_engine* e) { return !e->win_full && (e->xf_mask || e->xf_hash); }
+bool win_xpos(const pii_engine* e) { return !e->win_full && (e->xf_mask || e->xf_hash || e->xf_fpe); }
 
 // the window findings arena holds at least `want` records; with win_xpos, so does the position array, with
 // win_xg the candidate bytes
@@ -6269,6 +6340,9 @@ int run_window(pii_engine* e, const Call& c) {
                 k_win_hash<<<(uint32_t)(ms / HASH_BLOCK) + 1, HASH_BLOCK, 0, c.st>>>(
                     R.xf_kind, e->d_hash_key, e->d_hash_mid, W, B, e->wfd, e->wfbase, e->wspan_offs, e->wpos, c.out_offs,
                     e->d_err, c.out);
+            if (e->xf_fpe)
+                k_win_fpe<<<(uint32_t)(ms / FPE_BLOCK) + 1, FPE_BLOCK, 0, c.st>>>(e->fpe, W, B, e->wfd, e->wfbase, e->wspan_offs,
+                                                                               e->wpos, c.out_offs, e->d_err, c.out);
         }
         // (the redaction stage with its post-passes, as run_pipeline's covers k_mask and k_hash)
         if (e->k.timing >= 1) HIPCHK(hipEventRecord(e->kev[3], c.st));
@@ -6408,6 +6482,14 @@ bool upload_rules(pii_engine* e, HostRules& H) {
         set(e->d_hash_key, H.off[TB_HASH_KEY]);
         set(e->d_hash_mid, H.off[TB_HASH_MID]);
     }
+    if (H.xf_fpe) {
+        e->fpe.xf_kind = R.xf_kind;
+        set(e->fpe.fpe, H.off[TB_FPE]);
+        set(e->fpe.key, H.off[TB_FPE_KEY]);
+        set(e->fpe.alpha, H.off[TB_FPE_ALPHA]);
+        set(e->fpe.te0, H.off[TB_FPE_TE0]);
+        e->fpe.nkeys = H.fpe_nkeys;
+    }
     e->excl_general = H.excl_general;
     if (H.excl_general) {
         set(e->xt.xoff, H.off[TB_XG_OFF]);
@@ -6472,6 +6554,7 @@ bool upload_rules(pii_engine* e, HostRules& H) {
     e->xf_src = H.xf_src;
     e->xf_mask = H.xf_mask;
     e->xf_hash = H.xf_hash;
+    e->xf_fpe = H.xf_fpe;
     e->window_ok = H.window_ok;
     e->window_xg_ok = H.window_xg_ok && H.excl_general;
     return true;

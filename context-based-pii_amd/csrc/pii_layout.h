@@ -72,6 +72,14 @@ constexpr uint32_t XF_SAME_LEN = 0x80000000u;
 constexpr int XF_MASK_WORDS = 8;
 constexpr int XF_HASH_KEY_WORDS = 16;
 constexpr uint32_t XF_HASH_LEN = 44;      // base64 of a SHA-256 digest
+// crypto_replace_ffx_fpe_config (pii_fpe.h).  A key record: Nr, the 4 * (Nr + 1) AES round-key words, zeros.
+// An alphabet record: radix, nmin, nmax, 0; the byte -> digit map [128] (0xff: outside the alphabet); the
+// digit -> byte map [96]; b(v), v = 1 .. 32, the bytes of radix^v - 1.  Per type: key | alphabet << 16.
+constexpr int XF_FPE_KEY_WORDS = 64;
+constexpr int XF_FPE_ALPHA_WORDS = 68;
+constexpr int XF_FPE_NMAX = 64;           // numerals at most (v <= 32, NUM(B) <= 16 bytes)
+constexpr int XF_FPE_KEYS_MAX = 16;       // distinct keys of one rule set (k_fpe keeps their round keys in LDS)
+constexpr int XF_FPE_TE0_WORDS = 256;     // the AES round table fpe_te0 builds (beside the keys in the rules buffer)
 
 // k_scan's table entries are absolute LDS byte addresses of the next row, bit 0 = accept (scan_tables);
 // k_scan has no static LDS, so its dynamic region starts at LDS address 0 and an entry IS the address

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/pii_engine.h"
+#include "pii_fpe.h"
 #include "pii_layout.h"
 
 namespace {
@@ -291,12 +292,13 @@ inline bool pack_image(const ImageParts& parts, uint32_t aux, HostImage& out) {
 // ------------------------------------------------------------------------------- host rules
 // the tables of the packed rules buffer, in the order they are placed (256-byte aligned sections); the
 // SCAN groups' tables follow TB_XF_MASK, the hash tables come after every other table (rules without a
-// hash type keep their layout), the general exclusion tables after those (likewise); the text exclusion
-// rules live in their kernel's image alone
+// hash type keep their layout), the general exclusion tables after those (likewise), the FPE tables after
+// those (likewise); the text exclusion rules live in their kernel's image alone
 enum { TB_CMAP4, TB_TD, TB_TK, TB_D_ACCID, TB_D_ACC_OFF, TB_D_ACC_IDS, TB_K_ACCID, TB_K_ACC_MIN, TB_D_NPAIR, TB_K_GRP,
        TB_D_NA, TB_DET_TYPE, TB_DET_VAL, TB_DET_LIK, TB_DET_EXIDX, TB_FIRST_DESC, TB_HOT_RULE, TB_HOT_DESC,
        TB_VAR_ENABLED, TB_VAR_MINLIK, TB_RULE_OFF, TB_RULE_IDS, TB_EXCL_OFF, TB_EXCL_IDS, TB_TOK_OFF, TB_TOK_BYTES,
-       TB_TOK_LEN, TB_XF_KIND, TB_XF_MASK, TB_HASH_KEY, TB_HASH_MID, TB_XG_OFF, TB_XG_IDS, TB_XG_IDX, TB_N };
+       TB_TOK_LEN, TB_XF_KIND, TB_XF_MASK, TB_HASH_KEY, TB_HASH_MID, TB_XG_OFF, TB_XG_IDS, TB_XG_IDX, TB_FPE, TB_FPE_KEY,
+       TB_FPE_ALPHA, TB_FPE_TE0, TB_N };
 enum { GT_CMAP4, GT_TD, GT_TK, GT_D_ACCID, GT_K_ACCID, GT_D_NPAIR, GT_N };
 
 // a SCAN group >= 1: its own D automaton and class map, a 1-row never-accepting K stub
@@ -327,7 +329,8 @@ struct HostRules {
     std::vector<std::string> names;
     std::vector<int> kw_type;
     std::vector<uint8_t> xf_kind;
-    bool xf_src = false, xf_mask = false, xf_hash = false;
+    bool xf_src = false, xf_mask = false, xf_hash = false, xf_fpe = false;
+    uint32_t fpe_nkeys = 0;            // the key records of xf.fpe_key (<= XF_FPE_KEYS_MAX)
     bool window_ok = false;
     bool window_xg_ok = false;         // general / text exclusion rules alone took window_ok (meta[15]; absent: no)
     // general exclusion rules (var.xg_off / var.xg_ids / det.xgidx): k_exclude decides them, the
@@ -419,6 +422,8 @@ struct HostXf {
     std::vector<uint32_t> maskp, tok_off, tok_len;
     std::string tok;
     View<uint32_t> hash_key, hash_mid;
+    View<uint32_t> fpe, fpe_key, fpe_alpha;
+    std::vector<uint32_t> fpe_te0;  // the AES table (fpe_te0), built here
 };
 struct GroupTabs {
     std::vector<uint16_t> td, dacc, npair;
@@ -593,6 +598,55 @@ inline bool read_text_exclusion(const Blob& B, const CoreSecs& c, HostExcl& x, H
     return true;
 }
 
+// crypto_replace_ffx_fpe_config (rules with an FPE type): xf.fpe, per type key | alphabet << 16; xf.fpe_key,
+// per key a record of XF_FPE_KEY_WORDS; xf.fpe_alpha, per alphabet a record of XF_FPE_ALPHA_WORDS (pii_layout.h).
+// Everything ff1_apply indexes by is checked here: the kernels check nothing.
+inline bool read_fpe(const Blob& B, HostXf& x, HostRules& H) {
+    const Why& bad = B.bad;
+    const size_t T = H.R.T;
+    if (!B.has("xf.fpe") || !B.has("xf.fpe_key") || !B.has("xf.fpe_alpha")) return bad("FPE sections are not all present");
+    if (!B.view("xf.fpe", x.fpe) || !B.view("xf.fpe_key", x.fpe_key) || !B.view("xf.fpe_alpha", x.fpe_alpha)) return false;
+    if (x.fpe.n != T) return bad("xf.fpe does not hold one word per type");
+    if (x.fpe_key.n == 0 || x.fpe_key.n % XF_FPE_KEY_WORDS != 0) return bad("xf.fpe_key does not hold whole key records");
+    if (x.fpe_alpha.n == 0 || x.fpe_alpha.n % XF_FPE_ALPHA_WORDS != 0)
+        return bad("xf.fpe_alpha does not hold whole alphabet records");
+    const size_t nk = x.fpe_key.n / XF_FPE_KEY_WORDS, na = x.fpe_alpha.n / XF_FPE_ALPHA_WORDS;
+    if (nk > (size_t)XF_FPE_KEYS_MAX) return bad("xf.fpe_key holds too many keys");
+    for (size_t t = 0; t < T; ++t) {
+        if (H.xf_kind[t] != PII_XF_FPE) continue;
+        if ((x.fpe[t] & 0xffffu) >= nk) return bad("xf.fpe names a key past the key table");
+        if ((x.fpe[t] >> 16) >= na) return bad("xf.fpe names an alphabet past the alphabet table");
+    }
+    for (size_t k = 0; k < nk; ++k) {
+        const uint32_t nr = x.fpe_key[k * XF_FPE_KEY_WORDS];
+        if (nr != 10 && nr != 12 && nr != 14) return bad("xf.fpe_key holds a round count that is not 10, 12 or 14");
+    }
+    for (size_t a = 0; a < na; ++a) {
+        const View<uint32_t> rec = x.fpe_alpha.sub(a * XF_FPE_ALPHA_WORDS, XF_FPE_ALPHA_WORDS);
+        const uint32_t radix = rec[0], nmin = rec[1], nmax = rec[2];
+        const uint8_t* to_digit = reinterpret_cast<const uint8_t*>(rec.p + 4);
+        const uint8_t *to_byte = to_digit + 128, *bv = to_byte + 96;
+        if (radix < 2 || radix > 95) return bad("xf.fpe_alpha holds a radix outside 2..95");
+        size_t inside = 0;
+        for (uint32_t c = 0; c < 128; ++c) {
+            if (to_digit[c] == 0xff) continue;
+            if (to_digit[c] >= radix || to_byte[to_digit[c]] != c) return bad("xf.fpe_alpha holds maps that are not inverse");
+            ++inside;
+        }
+        for (uint32_t d = 0; d < radix; ++d)
+            if (to_byte[d] > 127 || to_digit[to_byte[d]] != d) return bad("xf.fpe_alpha holds maps that are not inverse");
+        if (inside != radix) return bad("xf.fpe_alpha holds maps that are not inverse");
+        if (nmin < 2 || nmin > nmax || nmax > (uint32_t)XF_FPE_NMAX) return bad("xf.fpe_alpha holds numeral limits out of range");
+        for (int v = 0; v < 32; ++v)
+            if (bv[v] == 0 || bv[v] > 16 || (v > 0 && bv[v] < bv[v - 1]))
+                return bad("xf.fpe_alpha holds byte lengths that are not ascending up to 16");
+    }
+    H.fpe_nkeys = (uint32_t)nk;
+    x.fpe_te0.resize(XF_FPE_TE0_WORDS);
+    pii::fpe_te0(x.fpe_te0.data());
+    return true;
+}
+
 // deidentify_config (without the sections every type is replaced by its "[NAME]" token) and the token
 // tables behind the output
 inline bool read_transformations(const Blob& B, HostXf& x, HostRules& H) {
@@ -608,11 +662,12 @@ inline bool read_transformations(const Blob& B, HostXf& x, HostRules& H) {
             !B.view("xf.mask", mask, T * XF_MASK_WORDS, ""))
             return bad(xf_bad);
         for (size_t t = 0; t < T; ++t) {
-            if (kind[t] > PII_XF_HASH || ro[t] > ro[t + 1] || ro[t + 1] > repl.n || ro[t + 1] - ro[t] > 255) return bad(xf_bad);
+            if (kind[t] > PII_XF_FPE || ro[t] > ro[t + 1] || ro[t + 1] > repl.n || ro[t + 1] - ro[t] > 255) return bad(xf_bad);
             H.xf_kind[t] = kind[t];
-            H.xf_src |= kind[t] == PII_XF_MASK || kind[t] == PII_XF_KEEP;
+            H.xf_src |= kind[t] == PII_XF_MASK || kind[t] == PII_XF_KEEP || kind[t] == PII_XF_FPE;
             H.xf_mask |= kind[t] == PII_XF_MASK;
             H.xf_hash |= kind[t] == PII_XF_HASH;
+            H.xf_fpe |= kind[t] == PII_XF_FPE;
         }
         if (H.xf_hash) {   // per type a key index, per key two midstates; a hash type's replacement is its placeholder
             if (!B.view("xf.hash_key", x.hash_key, T, "") || !B.view("xf.hash_mid", x.hash_mid) || x.hash_mid.n == 0 ||
@@ -623,6 +678,7 @@ inline bool read_transformations(const Blob& B, HostXf& x, HostRules& H) {
                     (x.hash_key[t] >= x.hash_mid.n / XF_HASH_KEY_WORDS || ro[t + 1] - ro[t] != XF_HASH_LEN))
                     return bad(xf_bad);
         }
+        if (H.xf_fpe && !read_fpe(B, x, H)) return false;
         std::copy(mask.p, mask.p + mask.n, x.maskp.begin());
         for (size_t t = 0; t < T; ++t)
             if (H.xf_kind[t] == PII_XF_MASK && (x.maskp[t * XF_MASK_WORDS] & 0xffu) > 127u) return bad(xf_bad);
@@ -637,7 +693,7 @@ inline bool read_transformations(const Blob& B, HostXf& x, HostRules& H) {
         else if (H.xf_kind[t] == PII_XF_REPLACE || H.xf_kind[t] == PII_XF_HASH)   // (hash: the placeholder)
             x.tok.append(reinterpret_cast<const char*>(repl.p) + ro[t], ro[t + 1] - ro[t]);
         x.tok_off[t + 1] = (uint32_t)x.tok.size();
-        const bool same_len = H.xf_kind[t] == PII_XF_MASK || H.xf_kind[t] == PII_XF_KEEP;
+        const bool same_len = H.xf_kind[t] == PII_XF_MASK || H.xf_kind[t] == PII_XF_KEEP || H.xf_kind[t] == PII_XF_FPE;
         x.tok_len[t] = same_len ? XF_SAME_LEN : x.tok_off[t + 1] - x.tok_off[t];
     }
     x.tok += "\n";               // the re-scan window separator (k_win_redact piece source)
@@ -759,6 +815,12 @@ inline void pack_rules(const CoreSecs& c, const HostExcl& x, const HostXf& xf, c
         H.off[TB_XG_OFF] = put(part(x.xg_off));
         H.off[TB_XG_IDS] = put(part(x.xg_ids));
         H.off[TB_XG_IDX] = put(part(x.xg_idx));
+    }
+    if (H.xf_fpe) {
+        H.off[TB_FPE] = put(part(xf.fpe));
+        H.off[TB_FPE_KEY] = put(part(xf.fpe_key));
+        H.off[TB_FPE_ALPHA] = put(part(xf.fpe_alpha));
+        H.off[TB_FPE_TE0] = put(part(xf.fpe_te0));
     }
 }
 

@@ -34,7 +34,7 @@ PII_WINDOW_FULL = 1
 PII_WINDOW_XF = 2
 PII_WINDOW_XG = 16    # (4 and 8 are not flags: pii_window_enable_ex answers PII_E_ARG)
 # pii_type_transform: what the rules' deidentify_config does with a finding of a type
-PII_XF_INFO_TYPE, PII_XF_REPLACE, PII_XF_REDACT, PII_XF_MASK, PII_XF_KEEP, PII_XF_HASH = range(6)
+PII_XF_INFO_TYPE, PII_XF_REPLACE, PII_XF_REDACT, PII_XF_MASK, PII_XF_KEEP, PII_XF_HASH, PII_XF_FPE = range(7)
 
 
 class PiiError(RuntimeError):

@@ -89,13 +89,19 @@ int pii_type_name(struct pii_engine* e, uint32_t t, char* buf, size_t cap);
  *   KEEP       no transformation applies: the bytes stay (the finding is still reported)
  *   HASH       crypto_hash_config: base64(HMAC-SHA256(key, finding bytes)), always 44 bytes.  The blob
  *              holds, per key, the two HMAC midstates (xf.hash_mid) instead of the key; they are as
- *              secret as the key */
+ *              secret as the key
+ *   FPE        crypto_replace_ffx_fpe_config: the finding's characters of the alphabet, encrypted among
+ *              themselves with FF1 over AES under an empty tweak; every other byte stays, so the byte
+ *              length is the finding's.  A finding with too few or too many such characters becomes
+ *              '*' bytes.  The blob holds, per key, the AES round keys (xf.fpe_key) instead of the key;
+ *              they are as secret as the key */
 #define PII_XF_INFO_TYPE 0
 #define PII_XF_REPLACE 1
 #define PII_XF_REDACT 2
 #define PII_XF_MASK 3
 #define PII_XF_KEEP 4
 #define PII_XF_HASH 5
+#define PII_XF_FPE 6
 int pii_type_transform(struct pii_engine* e, uint32_t t);
 /* name of the context group `g` (its expected_pii_type) */
 int pii_context_group_type(struct pii_engine* e, uint32_t g);
@@ -295,15 +301,15 @@ int pii_exclusion_mode(struct pii_engine* e);
  * and SCAN groups, tables in LDS or read in place); otherwise (a '\n'-consuming detector) by a FULL
  * re-scan -- the ring then keeps the raw text, every row's "\n"-joined window is materialised in HBM
  * and run through the scan+redact pipeline (one host wait per call for the joined size).  Rules with a
- * PII_XF_MASK, PII_XF_KEEP or PII_XF_HASH type (output bytes taken or computed from the text) also
+ * PII_XF_MASK, PII_XF_KEEP, PII_XF_HASH or PII_XF_FPE type (output bytes taken or computed from the text) also
  * take the FULL re-scan, unless the window is enabled with PII_WINDOW_XF; so do rules of
  * PII_EXCLUSION_GENERAL (general or text exclusion rules), unless it is enabled with PII_WINDOW_XG:
  *     full = (flags & PII_WINDOW_FULL)
- *            || (a mask / keep / hash type && !(flags & PII_WINDOW_XF))
+ *            || (a mask / keep / hash / FPE type && !(flags & PII_WINDOW_XF))
  *            || a detector consumes '\n' or tests a text edge
  *            || (general or text exclusion rules && !(flags & PII_WINDOW_XG))
- * With PII_WINDOW_XF a mask / keep finding's bytes are copied from its resident entry, then one thread per
- * window finding masks its code points or computes its surrogate over the placeholder (a surrogate is
+ * With PII_WINDOW_XF a mask / keep / FPE finding's bytes are copied from its resident entry, then one thread per
+ * window finding masks its code points, encrypts in place or computes its surrogate over the placeholder (a surrogate is
  * computed again in every window that holds the finding).  With PII_WINDOW_XG each window decides the
  * exclusions again over its resident candidates: an excluder occurrence is itself a resident candidate of
  * the same utterance, so per window candidate one byte of work buffer (likelihood under the window's
@@ -317,7 +323,7 @@ int pii_exclusion_mode(struct pii_engine* e);
  * PII_EXCLUSION_STREAMING or on a blob compiled before the flag existed (FULL). */
 #define PII_WINDOW_MAX 8
 #define PII_WINDOW_FULL 1   /* pii_window_enable_ex flag / pii_window_mode result: full re-scan */
-#define PII_WINDOW_XF 2     /* pii_window_enable_ex flag: mask / keep / hash types do not force the full re-scan */
+#define PII_WINDOW_XF 2     /* pii_window_enable_ex flag: mask / keep / hash / FPE types do not force the full re-scan */
 #define PII_WINDOW_XG 16    /* pii_window_enable_ex flag: general / text exclusion rules do not force the full re-scan
                              * (bits 4 and 8 are not flags: PII_E_ARG, as they have always been) */
 /* allocate the per-slot window history (n_conv_slots * slot_bytes of HBM); window_n <= PII_WINDOW_MAX,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the window re-scan costs under mask, keep and hash transformations, FULL against incremental
+"""What the window re-scan costs under mask, keep, hash and FPE transformations, FULL against incremental
 (PII_WINDOW_XF).
 
 The config-3-shaped stream of bench.py --workload window (one new row of every conversation per call, the
@@ -10,12 +10,13 @@ pii_last_timings [5]) and its median.  Configurations:
     shipped      the shipped rules, incremental: the floor
     A, B, H, HC  tests/xform_configs.py and tests/xform_hash_ref.py; each in FULL (what an engine enabled
                  without the flag runs; --full-repeats times, for the spread of repeated runs) and with the flag
+    F, FC        tests/xform_fpe_ref.py (crypto_replace_ffx_fpe_config), likewise; asked for with --rules
 
 The window bytes, output offsets and spans of every timed call of a flagged run are compared, on the GPU, with
 those of the same rules' FULL run; a difference ends the tool.  One JSON line per run and a summary line per
 rule set.  --profile re-runs the flagged configurations in a child process under
 `rocprofv3 --kernel-trace --stats` (counters are not collected) and adds one line with the average time per
-call of the window kernels, k_win_pos, k_win_mask and k_win_hash among them.
+call of the window kernels, k_win_pos, k_win_mask, k_win_hash and k_win_fpe among them.
 
     python tools/window_xf_cost.py [--conversations 100000] [--calls 10] [--rules A,B,H,HC] [--full-repeats 2]
                                    [--profile] [--out profiles/window_xf/xf_cost.jsonl]
@@ -38,7 +39,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 KERNELS = ("k_win_cands", "k_win_halo", "k_win_plan", "k_win_select", "k_win_alloc", "k_win_redact", "k_win_pos",
-           "k_win_mask", "k_win_hash", "k_win_commit", "k_scan_lb")
+           "k_win_mask", "k_win_hash", "k_win_fpe", "k_win_commit", "k_scan_lb")
 
 
 def pkg(mod):
@@ -47,7 +48,8 @@ def pkg(mod):
 
 def blocks():
     X, HR = importlib.import_module("xform_configs"), importlib.import_module("xform_hash_ref")
-    return X, {"shipped": None, "A": X.A, "B": X.B, "H": HR.H, "HC": HR.HC}
+    FR = importlib.import_module("xform_fpe_ref")
+    return X, {"shipped": None, "A": X.A, "B": X.B, "H": HR.H, "HC": HR.HC, "F": FR.F, "FC": FR.FC}
 
 
 def run(a, out):
