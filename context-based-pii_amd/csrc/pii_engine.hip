@@ -27,6 +27,7 @@
 //   k_hash         crypto_hash_config: HMAC-SHA256 surrogates over k_redact's placeholders (rules with a hash type)
 //   k_fpe          crypto_replace_ffx_fpe_config: FF1 over the findings k_redact<true> copied (rules with an FPE type)
 //   k_ctx_commit   write the per-conversation context back (only when the call succeeded)
+// pii_reidentify* (a call of its own): k_reid_check, a scan, k_reid_pos, k_reid (FF1 decryption of the FPE spans)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -3808,6 +3809,73 @@ __global__ __launch_bounds__(FPE_BLOCK) void k_fpe(const FpeTabs F, const uint8_
     fpe_span(F, s, t, text + offs[0] + r.in_lo, (int)(r.in_hi - r.in_lo), out + rs_out(r));
 }
 
+// ------------------------------------------------------------------------------- pii_reidentify
+// The inverse of the FPE types over de-identified rows, given the span list the de-identify call returned
+// (input coordinates, ordered by (utt, start)).  Span k's output range starts at start_k + D_k, D_k = the sum of
+// out_len - in_len over the earlier spans of its row, and is out_len(type_k, end_k - start_k) long.
+//   k_reid_check   one thread per span: well-formed and ordered after its predecessor, else PII_REID_BAD_SPAN;
+//                  its length delta (mod 2^32).  Thread 0 also holds the declared batch against the offsets.
+//   exclusive_scan the deltas' prefix over the whole list
+//   k_reid_pos     one thread per span: its row's first span by a lower bound on utt, its output position
+//                  (32-bit), and the test that its output range lies inside its row
+//   k_reid         one thread per span of an FPE type: ff1_apply<true> over the output range, in place
+// Each kernel leaves when the status word is set, so a bad span anywhere leaves every row as it was given.
+__global__ __launch_bounds__(256) void k_reid_check(const pii_span* __restrict__ sp, uint32_t n_spans,
+                                                    const uint64_t* __restrict__ offs, uint32_t n_utt, uint64_t base,
+                                                    uint64_t bytes, uint32_t n_types, const uint32_t* __restrict__ tok_len,
+                                                    uint32_t* __restrict__ delta, uint32_t* __restrict__ status) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k == 0 && (offs[0] != base || offs[n_utt] - offs[0] != bytes)) atomicOr(status, PII_REID_BAD_ARGS);
+    if (k >= n_spans) return;
+    const pii_span s = sp[k];
+    bool ok = s.utt < n_utt && s.info_type < n_types && s.start < s.end;
+    if (k > 0) {
+        const pii_span p = sp[k - 1];
+        ok = ok && (s.utt > p.utt || (s.utt == p.utt && s.start >= p.end));
+    }
+    delta[k] = ok ? out_len(tok_len, s.info_type, s.end - s.start) - (s.end - s.start) : 0u;
+    if (!ok) atomicOr(status, PII_REID_BAD_SPAN);
+}
+
+__global__ __launch_bounds__(256) void k_reid_pos(const pii_span* __restrict__ sp, uint32_t n_spans,
+                                                  const uint64_t* __restrict__ offs, uint64_t bytes,
+                                                  const uint32_t* __restrict__ tok_len, const uint64_t* __restrict__ pre,
+                                                  uint32_t* __restrict__ pos, uint32_t* __restrict__ status) {
+    if (*status != 0) return;
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_spans) return;
+    const pii_span s = sp[k];
+    uint32_t lo = 0, hi = (uint32_t)k;            // the first span of row s.utt (the list is ordered by utt)
+    while (lo < hi) {
+        const uint32_t m = lo + ((hi - lo) >> 1);
+        if (sp[m].utt < s.utt) lo = m + 1;
+        else hi = m;
+    }
+    const uint32_t p = s.start + (uint32_t)(pre[k] - pre[lo]);
+    const uint64_t r0 = offs[s.utt] - offs[0], r1 = offs[s.utt + 1] - offs[0];
+    pos[k] = p;
+    if (r0 > r1 || r1 > bytes || (uint64_t)p + out_len(tok_len, s.info_type, s.end - s.start) > r1 - r0)
+        atomicOr(status, PII_REID_BAD_SPAN);
+}
+
+// (rows: the output, which holds the de-identified rows; in and o of the body are the same bytes, so neither
+// is declared __restrict__)
+__global__ __launch_bounds__(FPE_BLOCK) void k_reid(const FpeTabs F, const pii_span* __restrict__ sp, uint32_t n_spans,
+                                                    const uint64_t* __restrict__ offs, const uint32_t* __restrict__ pos,
+                                                    const uint32_t* __restrict__ status, uint8_t* rows) {
+    __shared__ FpeLds s;
+    if (*status != 0) return;
+    fpe_stage(F, s);
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_spans) return;
+    const pii_span f = sp[k];
+    if (F.xf_kind[f.info_type] != PII_XF_FPE) return;
+    uint8_t* p = rows + (offs[f.utt] - offs[0]) + pos[k];
+    const uint32_t ka = F.fpe[f.info_type];
+    ff1_apply<true>(s.te0, s.key + (ka & 0xffffu) * XF_FPE_KEY_WORDS, F.alpha + (size_t)(ka >> 16) * XF_FPE_ALPHA_WORDS, p,
+                    (int)(f.end - f.start), p, s.num + threadIdx.x, FPE_BLOCK);
+}
+
 // per-info-type totals of the redact tiles' histograms (one atomic per type, no same-address storms)
 __global__ __launch_bounds__(256) void k_hist_reduce(const uint32_t* __restrict__ hist_part, uint32_t n_tiles, int T,
                                                      const uint32_t* __restrict__ err,
@@ -5371,6 +5439,15 @@ struct pii_engine {
     uint32_t* tile_first = nullptr;
     uint64_t cap_tiles = 0;
     uint32_t hist_types = 0;           // types counted per workgroup in LDS (k_spans)
+    // pii_reidentify*: per span its length delta, the deltas' prefix and its output position; the host form's
+    // staged rows (re-identified in place), offsets and spans, and its status word
+    uint32_t *rd_delta = nullptr, *rd_pos = nullptr, *rd_status = nullptr;
+    uint64_t* rd_pre = nullptr;
+    uint64_t rd_cap = 0, rd_cap_bytes = 0;
+    uint8_t* rd_rows = nullptr;
+    uint64_t* rd_offs = nullptr;
+    pii_span* rd_spans = nullptr;
+    uint32_t rd_cap_utt = 0, rd_cap_hspans = 0;
 };
 
 #define HIPCHK(x)                                                                  \
@@ -7323,6 +7400,102 @@ int pii_histogram_reset(pii_engine* e) {
     if (!e) return PII_E_ARG;
     e->h_hist_valid = false;
     e->hist_zero_pending = true;
+    return PII_OK;
+}
+
+// Re-identification.  Self-contained: its own status word (the caller's, or rd_status for the host form) and
+// its own work buffers; of the engine's state it reads the rules, and it shares the scans' tile states and
+// block sums in stream order.  No totals, no histogram, no call record: a pii_sync after it reports the call
+// before it.
+int pii_reidentify_device(pii_engine* e, const uint8_t* d_bytes, const uint64_t* d_offsets, uint32_t n_utt,
+                          uint64_t batch_base, uint64_t batch_bytes, const pii_span* d_spans, uint32_t n_spans,
+                          uint8_t* d_out_bytes, uint64_t out_cap, uint32_t* d_status, void* stream) {
+    if (!e || !d_offsets || !d_status || (n_spans && !d_spans) || (batch_bytes && (!d_bytes || !d_out_bytes)))
+        return PII_E_ARG;
+    if (batch_bytes > PII_MAX_BATCH_BYTES) {
+        e->err = "batch larger than PII_MAX_BATCH_BYTES (positions are 32-bit); split it";
+        return PII_E_ARG;
+    }
+    if (out_cap < batch_bytes) return PII_E_CAPACITY;
+    const uint8_t* src = d_bytes + batch_base;
+    const bool in_place = d_out_bytes == src;
+    if (!in_place && batch_bytes && d_out_bytes < src + batch_bytes && src < d_out_bytes + batch_bytes) {
+        e->err = "pii_reidentify_device: the output overlaps the rows without being the rows (d_bytes + batch_base)";
+        return PII_E_ARG;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e->stream;
+    int rc;
+    if ((uint64_t)n_spans + 1 > e->rd_cap) {
+        const uint64_t n = std::max<uint64_t>((uint64_t)n_spans + n_spans / 8 + 16, 4096);
+        if ((rc = grow(e, e->rd_delta, n)) || (rc = grow(e, e->rd_pos, n)) || (rc = grow(e, e->rd_pre, n + 1))) return rc;
+        e->rd_cap = n;
+    }
+    if (n_spans > e->cap_bsum) {          // exclusive_scan's block sums (shared with the scan calls' scans)
+        if ((rc = grow(e, e->bsum, 2 * ((size_t)n_spans / SCAN_TILE + 4)))) return rc;
+        e->cap_bsum = n_spans;
+    }
+    HIPCHK(hipMemsetAsync(d_status, 0, sizeof(uint32_t), st));
+    if (!in_place && batch_bytes) HIPCHK(hipMemcpyAsync(d_out_bytes, src, batch_bytes, hipMemcpyDeviceToDevice, st));
+    const uint32_t nb = n_spans / 256 + 1;
+    k_reid_check<<<nb, 256, 0, st>>>(d_spans, n_spans, d_offsets, n_utt, batch_base, batch_bytes, (uint32_t)e->R.T,
+                                     e->R.tok_len, e->rd_delta, d_status);
+    if (n_spans) {
+        if ((rc = exclusive_scan(e, e->rd_delta, n_spans, e->rd_pre, st))) return rc;
+        k_reid_pos<<<nb, 256, 0, st>>>(d_spans, n_spans, d_offsets, batch_bytes, e->R.tok_len, e->rd_pre, e->rd_pos, d_status);
+        if (e->xf_fpe)
+            k_reid<<<n_spans / FPE_BLOCK + 1, FPE_BLOCK, 0, st>>>(e->fpe, d_spans, n_spans, d_offsets, e->rd_pos, d_status,
+                                                                 d_out_bytes);
+    }
+    HIPCHK(hipGetLastError());
+    return PII_OK;
+}
+
+int pii_reidentify(pii_engine* e, const uint8_t* bytes, const uint64_t* offsets, uint32_t n_utt, const pii_span* spans,
+                   uint32_t n_spans, uint8_t* out_bytes, uint64_t out_cap) {
+    if (!e || !offsets || (n_spans && !spans)) return PII_E_ARG;
+    for (uint32_t i = 0; i < n_utt; ++i)
+        if (offsets[i + 1] < offsets[i]) return PII_E_ARG;
+    const uint64_t base = offsets[0], total = offsets[n_utt] - base;
+    if (total && (!bytes || !out_bytes)) return PII_E_ARG;
+    if (out_cap < total) return PII_E_CAPACITY;
+    HIPCHK(hipSetDevice(e->device));
+    int rc;
+    if (total + 16 > e->rd_cap_bytes) {
+        const uint64_t nb = total + total / 8 + 64;
+        if ((rc = grow(e, e->rd_rows, nb))) return rc;
+        e->rd_cap_bytes = nb;
+    }
+    if (n_utt + 1 > e->rd_cap_utt) {
+        const uint32_t nu = n_utt + n_utt / 8 + 64;
+        if ((rc = grow(e, e->rd_offs, (size_t)nu + 1))) return rc;
+        e->rd_cap_utt = nu;
+    }
+    if (n_spans > e->rd_cap_hspans) {
+        const uint32_t ns = n_spans + n_spans / 8 + 64;
+        if ((rc = grow(e, e->rd_spans, ns))) return rc;
+        e->rd_cap_hspans = ns;
+    }
+    if (!e->rd_status && (rc = grow(e, e->rd_status, 1))) return rc;
+    hipStream_t st = e->stream;
+    std::vector<uint64_t> rel(n_utt + 1);
+    for (uint32_t i = 0; i <= n_utt; ++i) rel[i] = offsets[i] - base;
+    if (total) HIPCHK(hipMemcpyAsync(e->rd_rows, bytes + base, total, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->rd_offs, rel.data(), ((size_t)n_utt + 1) * 8, hipMemcpyHostToDevice, st));
+    if (n_spans) HIPCHK(hipMemcpyAsync(e->rd_spans, spans, (size_t)n_spans * sizeof(pii_span), hipMemcpyHostToDevice, st));
+    uint32_t status = 0;
+    rc = pii_reidentify_device(e, e->rd_rows, e->rd_offs, n_utt, 0, total, e->rd_spans, n_spans, e->rd_rows, e->rd_cap_bytes,
+                               e->rd_status, st);
+    if (!rc) HIPCHK(hipMemcpyAsync(&status, e->rd_status, sizeof(status), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));          // (rel and status are read and written until here)
+    if (rc) return rc;
+    if (status) {
+        if (total && out_bytes != bytes + base) std::memmove(out_bytes, bytes + base, total);
+        e->err = "pii_reidentify: a span is malformed (utt < n_utt, info_type < n_types, start < end), not ordered by "
+                 "(utt, start) without overlap, or its output range start + D .. + out_len leaves its row";
+        return PII_E_ARG;
+    }
+    if (total) HIPCHK(hipMemcpy(out_bytes, e->rd_rows, total, hipMemcpyDeviceToHost));
     return PII_OK;
 }
 

@@ -1,6 +1,6 @@
-// crypto_replace_ffx_fpe_config: FF1 (NIST SP 800-38G) over AES (FIPS-197) under an empty tweak, encryption
-// only.  One body, ff1_apply, for the batch post-pass (k_fpe) and the window post-pass (k_win_fpe), which only
-// locate their finding and stage the tables.  It is written in plain C++ with every table behind a pointer
+// crypto_replace_ffx_fpe_config: FF1 (NIST SP 800-38G) over AES (FIPS-197) under an empty tweak.  One body,
+// ff1_apply, for the batch post-pass (k_fpe), the window post-pass (k_win_fpe) and, in its decrypt form
+// ff1_apply<true>, pii_reidentify (k_reid); the kernels only locate their finding and stage the tables.  It is written in plain C++ with every table behind a pointer
 // and no device builtin, so the same text compiles for the host: tests/fpe_body_main.cpp runs it on the CPU
 // under the sanitizers.  In the kernels te0, the key record and the numerals live in LDS, the alphabet record
 // in the rules buffer.  Nothing here is indexed at run time but those tables: the cipher state, the limbs of
@@ -96,6 +96,13 @@ PII_FPE_FN void fpe_div(uint32_t& w, uint32_t& rem, uint32_t r, uint32_t mul) {
 // change roles, so after the ten rounds X stands in place.  c = (NUM(A) + y) mod radix^m needs no modulus:
 // y mod radix^m is y's low m digits, m short divisions of y's five limbs, each added to A's numeral with the
 // carry; the carry out of the top numeral is dropped.
+//
+// DEC: the inverse (Algorithm 8), called with in == o (in[i] is read before o[i] is written).  The rounds run
+// i = 9 .. 0; round i's A-slot and B-slot are the ones encryption round i used, so the A-slot holds what that
+// round wrote, y comes from the B-slot as above, and the A-slot becomes (A - y mod radix^m) mod radix^m: the
+// same remainders, subtracted with a borrow that is dropped out of the top numeral.  With n out of range the
+// decrypt form writes nothing: a fail-closed "***" stays "***", a re-identify never destroys text.
+template <bool DEC = false>
 PII_FPE_FN void ff1_apply(const uint32_t* te0, const uint32_t* key, const uint32_t* alpha, const uint8_t* in,
                           const int len, uint8_t* o, uint8_t* num, const int stride) {
     const uint32_t radix = alpha[0], nmin = alpha[1], nmax = alpha[2];
@@ -111,7 +118,8 @@ PII_FPE_FN void ff1_apply(const uint32_t* te0, const uint32_t* key, const uint32
         }
     }
     if (n < nmin || n > nmax) {
-        for (int i = 0; i < len; ++i) o[i] = '*';
+        if (!DEC)
+            for (int i = 0; i < len; ++i) o[i] = '*';
         return;
     }
     const uint32_t u = n >> 1, v = n - u;
@@ -119,7 +127,8 @@ PII_FPE_FN void ff1_apply(const uint32_t* te0, const uint32_t* key, const uint32
     const uint32_t mul = 0xffffffffu / radix + 1u;
     uint32_t p0 = 0x01020100u, p1 = radix << 16 | 10u << 8 | (u & 255u), p2 = n, p3 = 0;
     aes_encrypt(te0, key, p0, p1, p2, p3);
-    for (uint32_t i = 0; i < 10; ++i) {
+    for (uint32_t rnd = 0; rnd < 10; ++rnd) {
+        const uint32_t i = DEC ? 9u - rnd : rnd;
         const bool even = (i & 1u) == 0;
         const uint32_t a0 = even ? 0 : u, m = even ? u : v;         // A = num[a0, a0 + m)
         const uint32_t b0 = even ? u : 0, bl = even ? v : u;        // B = num[b0, b0 + bl)
@@ -169,10 +178,16 @@ PII_FPE_FN void ff1_apply(const uint32_t* te0, const uint32_t* key, const uint32
             fpe_div(y1, rem, radix, mul);
             fpe_div(y0, rem, radix, mul);
             uint8_t* a = num + (a0 + m - 1u - k) * stride;
-            uint32_t s = *a + rem + carry;
-            carry = s >= radix ? 1u : 0u;
-            s -= carry ? radix : 0u;
-            *a = (uint8_t)s;
+            if (DEC) {
+                const int32_t s = (int32_t)*a - (int32_t)rem - (int32_t)carry;      // carry: the borrow
+                carry = s < 0 ? 1u : 0u;
+                *a = (uint8_t)(s + (carry ? (int32_t)radix : 0));
+            } else {
+                uint32_t s = *a + rem + carry;
+                carry = s >= radix ? 1u : 0u;
+                s -= carry ? radix : 0u;
+                *a = (uint8_t)s;
+            }
         }
     }
     uint32_t k = 0;

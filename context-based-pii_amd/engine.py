@@ -29,7 +29,8 @@ EXPORTS = ["pii_engine_create", "pii_engine_destroy", "pii_engine_info", "pii_ty
            "pii_rescan_window_device_ex", "pii_scan_redact_ext", "pii_scan_redact_device_ext", "pii_window_enable_ex",
            "pii_window_mode", "pii_set_scratch_limit", "pii_scratch_bytes", "pii_context_resize",
            "pii_context_update", "pii_set_timing", "pii_type_transform", "pii_exclusion_mode",
-           "pii_rescan_window_ext", "pii_rescan_window_device_ext"]
+           "pii_rescan_window_ext", "pii_rescan_window_device_ext", "pii_reidentify", "pii_reidentify_device"]
+PII_REID_BAD_SPAN, PII_REID_BAD_ARGS = 1, 2      # *d_status of pii_reidentify_device
 PII_WINDOW_FULL = 1
 PII_WINDOW_XF = 2
 PII_WINDOW_XG = 16    # (4 and 8 are not flags: pii_window_enable_ex answers PII_E_ARG)
@@ -120,6 +121,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.pii_rescan_window_device_ex.argtypes = lib.pii_scan_redact_device_ex.argtypes
     lib.pii_rescan_window_ext.argtypes = lib.pii_scan_redact_ext.argtypes
     lib.pii_rescan_window_device_ext.argtypes = lib.pii_scan_redact_device_ext.argtypes
+    lib.pii_reidentify.argtypes = [P, P, P, c.c_uint32, P, c.c_uint32, P, c.c_uint64]
+    lib.pii_reidentify_device.argtypes = [P, P, P, c.c_uint32, c.c_uint64, c.c_uint64, P, c.c_uint32, P, c.c_uint64, P, P]
     for name in EXPORTS:
         if name != "pii_last_error":
             getattr(lib, name).restype = c.c_int
@@ -380,6 +383,34 @@ class Engine:
                                                  d_ext, d_ext_n, ext_stride, stream)
         if rc != PII_OK:
             raise self._err(rc, "pii_scan_redact_device_ext")
+
+    # ------------------------------------------------------------------ re-identification
+    def reidentify(self, texts: Sequence[bytes], spans: np.ndarray) -> List[bytes]:
+        """The inverse of the FPE types (pii_reidentify): texts are de-identified rows, spans the SPAN_DTYPE
+        list the de-identify call returned for them -- BatchResult.spans as it is, or a slice of whole rows
+        with utt renumbered from 0 by the caller.  Returns the rows with every FPE surrogate decrypted; every
+        other byte stays, so each row keeps its length.  The engine must hold the rules that de-identified
+        the rows.  A rescan_window result works as it is: its spans are relative to the joined window, and
+        so are its output rows.  A malformed list raises PiiError(PII_E_ARG)."""
+        data, offs = pack(texts)
+        n = len(texts)
+        sp = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
+        out = np.empty(max(1, int(offs[-1])), dtype=np.uint8)
+        rc = self.lib.pii_reidentify(self.h, _ptr(data) if len(data) else None, _ptr(offs), n,
+                                     _ptr(sp) if len(sp) else None, len(sp), _ptr(out), int(offs[-1]))
+        if rc != PII_OK:
+            raise self._err(rc, "pii_reidentify")
+        return [out[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+
+    def reidentify_device(self, d_bytes, d_offsets, n_utt, batch_base, batch_bytes, d_spans, n_spans, d_out,
+                          out_cap, d_status, stream=None) -> None:
+        """pii_reidentify_device: all pointers are device memory; enqueues on `stream` without a wait or a
+        device-to-host read.  *d_status becomes 0, or PII_REID_* bits with d_out an unchanged copy of the rows.
+        d_out == d_bytes + batch_base re-identifies in place."""
+        rc = self.lib.pii_reidentify_device(self.h, d_bytes, d_offsets, n_utt, batch_base, batch_bytes, d_spans,
+                                            n_spans, d_out, out_cap, d_status, stream)
+        if rc != PII_OK:
+            raise self._err(rc, "pii_reidentify_device")
 
     def reserve(self, max_utt: int, max_bytes: int, max_out: int, max_spans: int) -> None:
         """pre-size the work buffers so calls within these bounds allocate nothing (pii_reserve)"""

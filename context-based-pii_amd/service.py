@@ -55,7 +55,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .engine import (PII_E_ARG, PII_E_CAPACITY, PII_E_DEVICE, PII_E_NOMEM, PII_E_ORDER, PII_E_RULES,
-                     ROLE_AGENT, ROLE_CUSTOMER, ROLE_OTHER, Engine, PiiError)
+                     ROLE_AGENT, ROLE_CUSTOMER, ROLE_OTHER, SPAN_DTYPE, Engine, PiiError)
 
 CONTEXT_TTL_SECONDS = 90          # main_service/main.py:163
 
@@ -379,12 +379,23 @@ class PiiService:
         return np.concatenate([self._context_fallback(texts[:h], slots[:h], roles[:h], ts[:h]),
                                self._context_fallback(texts[h:], slots[h:], roles[h:], ts[h:])])
 
-    def _without_slots(self, part, slots, code, texts, ts, call, window=False) -> List[str]:
+    def _findings(self, res, n: int) -> List[List[dict]]:
+        """a call's spans as per-row findings: byte offsets into the UTF-8 of the row's text, the type's name"""
+        rows: List[List[dict]] = [[] for _ in range(n)]
+        for u, s, e, t in zip(res.spans["utt"].tolist(), res.spans["start"].tolist(), res.spans["end"].tolist(),
+                              res.spans["info_type"].tolist()):
+            rows[u].append({"start": s, "end": e, "info_type": self.engine.type_names[t]})
+        return rows
+
+    def _without_slots(self, part, slots, code, texts, ts, call, window=False,
+                       findings: Optional[list] = None) -> List[str]:
         """A run some of whose conversations got no slot (SlotMap.assign): those rows get the
         reference's error string and store nothing; the other rows run as usual (dropping whole
-        conversations keeps the batch contract).  Called with the service lock held."""
+        conversations keeps the batch contract).  Called with the service lock held.  findings: a list that
+        receives one entry per row (process_batch)."""
         keep = [k for k, sl in enumerate(slots) if sl is not None]
         red: Dict[int, str] = {k: error_string(code, part[k]["text"]) for k in range(len(part)) if slots[k] is None}
+        found: Dict[int, Optional[list]] = {}
         if keep:
             k_texts = [texts[k] for k in keep]
             k_slots = [slots[k] for k in keep]
@@ -402,6 +413,10 @@ class PiiService:
                         self.slots.note_window(sl)
                 self._note(k_slots, k_roles, [part[k]["text"] for k in keep], k_ts, res.ctx_info)
                 red.update({k: _dec(res.text(j)) for j, k in enumerate(keep)})
+                if findings is not None:
+                    found.update(zip(keep, self._findings(res, len(keep))))
+        if findings is not None:
+            findings.extend(found.get(k) for k in range(len(part)))
         return [red[k] for k in range(len(part))]
 
     # ---------------------------------------------------------------- reference seam (main.py:580)
@@ -663,12 +678,17 @@ class PiiService:
                 self._evict(slot)
 
     # ---------------------------------------------------------------- batched ingest
-    def process_batch(self, rows: Sequence[dict]) -> List[str]:
+    def process_batch(self, rows: Sequence[dict], findings: Optional[list] = None) -> List[str]:
         """Pub/Sub-shaped rows {conversation_id, participant_role ('AGENT' | 'END_USER' | ...),
         text, start_timestamp_usec}, grouped by conversation in entry order -> redacted texts.
         Agent rows update their conversation's context exactly as handle_agent_utterance would;
         other roles are redacted without context.  Never raises for engine errors: a failed
-        engine call yields the reference's error strings for its rows (main.py:752-773)."""
+        engine call yields the reference's error strings for its rows (main.py:752-773).
+
+        findings: a list that receives one entry per row, in row order: the row's findings as
+        [{"start", "end", "info_type"}] (byte offsets into the UTF-8 of the row's text, the type as its
+        name), or None for a row whose engine call failed.  Kept with the redacted text they are what
+        reidentify_batch needs to restore the FPE surrogates later."""
         out: List[str] = []
         for run in self._sub_batches([r["conversation_id"] for r in rows]):
             with self.lock:
@@ -680,7 +700,7 @@ class PiiService:
                 now = self._now_us()
                 slots, code = self.slots.assign([r["conversation_id"] for r in part], pinned, now)
                 if code:
-                    out.extend(self._without_slots(part, slots, code, texts, ts, self._run))
+                    out.extend(self._without_slots(part, slots, code, texts, ts, self._run, findings=findings))
                     continue
                 roles = [role_code(r.get("participant_role")) for r in part]
                 try:
@@ -690,9 +710,38 @@ class PiiService:
                     self._note(slots, roles, [r["text"] for r in part], ts,
                                self._context_fallback(texts, slots, roles, ts))
                     out.extend(error_string(e.code, r["text"]) for r in part)
+                    if findings is not None:
+                        findings.extend(None for _ in part)
                     continue
                 self._note(slots, roles, [r["text"] for r in part], ts, res.ctx_info)
                 out.extend(_dec(res.text(i)) for i in range(len(part)))
+                if findings is not None:
+                    findings.extend(self._findings(res, len(part)))
+        return out
+
+    def reidentify_batch(self, items: Sequence[dict]) -> List[str]:
+        """The way back for crypto_replace_ffx_fpe_config surrogates: items are [{"text": a de-identified
+        text process_batch returned, "findings": its entry of process_batch's findings list}], the result the
+        texts with every FPE surrogate decrypted (Engine.reidentify); tokens, masks, hashes and removed
+        findings stay as they are.  An item whose findings are None (its de-identification failed: the text
+        is an error string) comes back unchanged.  The engine must hold the rules that de-identified the
+        texts.  A malformed finding raises PiiError: it is a caller bug, not an engine outage."""
+        out = [it["text"] for it in items]
+        live = [i for i, it in enumerate(items) if it.get("findings") is not None]
+        if not live:
+            return out
+        type_of = {n: t for t, n in enumerate(self.engine.type_names)}
+        recs = []
+        for u, i in enumerate(live):
+            for f in items[i]["findings"]:
+                if f["info_type"] not in type_of:
+                    raise PiiError(PII_E_ARG, f"reidentify_batch: unknown info type {f['info_type']!r}")
+                recs.append((u, f["start"], f["end"], type_of[f["info_type"]], 0, 0))
+        spans = np.array(recs, dtype=SPAN_DTYPE) if recs else np.zeros(0, dtype=SPAN_DTYPE)
+        with self.lock:
+            restored = self.engine.reidentify([_enc(items[i]["text"]) for i in live], spans)
+        for i, b in zip(live, restored):
+            out[i] = _dec(b)
         return out
 
     # ---------------------------------------------------------------- Pub/Sub stream formats (§8(f))

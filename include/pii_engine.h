@@ -396,6 +396,50 @@ int pii_rescan_window_device_ext(struct pii_engine* e, const uint8_t* d_bytes, c
                                  pii_span* d_spans, uint32_t span_cap, int16_t* d_win_ctx,
                                  const pii_span* d_ext, const uint32_t* d_ext_n, uint32_t ext_stride, void* stream);
 
+/* ---------------------------------------------------------------- re-identification
+ * The inverse of PII_XF_FPE: FF1 decryption (SP 800-38G Algorithm 8, empty tweak) of the surrogates in rows a
+ * pii_scan_redact* or pii_rescan_window* call de-identified.  The inputs are those rows and the span list that
+ * call returned for them, unchanged: spans in the coordinates of that call's INPUT, ordered by (utt, start)
+ * (a slice of whole rows with utt renumbered from 0 is such a list too).  The engine does the coordinate
+ * arithmetic: span k of row u was written at
+ *     start_k + D_k,  D_k = sum over the earlier spans j of row u of out_len_j - (end_j - start_j),
+ * out_len_j bytes long: the finding's own length for MASK / KEEP / FPE, the token, the replacement, 0 or 44
+ * for the others.  A span of an FPE type is decrypted there in place; every other byte of the row stays, so
+ * every row keeps its length and the output is packed as the input is.  A surrogate whose count of alphabet
+ * characters is outside the alphabet's limits (the fail-closed '*' run among them) stays as it is: the call
+ * never destroys text.  Only FPE is reversed; tokens, masks and hashes stay.
+ *
+ * The engine must be created from the blob that de-identified the rows.  The AES round keys that blob already
+ * holds (xf.fpe_key) are what makes the call possible: nothing new is secret, and whoever holds the blob can
+ * reverse its surrogates.
+ *
+ * An engine whose rules have no FPE type checks the spans and copies the rows.  n_utt == 0, n_spans == 0 and
+ * empty rows are valid.  The calls touch neither the conversation context, the window history, the histogram
+ * nor what pii_sync reports or re-runs: a pii_sync after them still answers for the scan call before them. */
+#define PII_REID_BAD_SPAN 1u  /* malformed, unordered or overlapping span, or one whose output range leaves its row */
+#define PII_REID_BAD_ARGS 2u  /* batch_base / batch_bytes do not match the offsets */
+
+/* Host buffers.  out_bytes receives the rows packed as the input is (offsets[i] - offsets[0] are the output's
+ * offsets; every row keeps its length); out_cap >= offsets[n_utt] - offsets[0], else PII_E_CAPACITY.
+ * Waits for the result.  A bad span -> PII_E_ARG with a pii_last_error text that names the rule, and
+ * out_bytes holds the rows unchanged. */
+int pii_reidentify(struct pii_engine* e, const uint8_t* bytes, const uint64_t* offsets, uint32_t n_utt,
+                   const pii_span* spans, uint32_t n_spans, uint8_t* out_bytes, uint64_t out_cap);
+
+/* Device buffers, enqueued on `stream` (NULL = the engine's), no wait, no device-to-host read.
+ * *d_status (device memory) becomes 0, or PII_REID_* bits with the output an unchanged copy of the rows.
+ * d_out_bytes == d_bytes + batch_base works in place and copies nothing; any other overlap of the two ranges
+ * is PII_E_ARG.  Like every call of an engine it is ordered with the others by the caller: it shares work
+ * buffers with them, so it runs on the stream they run on, or after they have finished.
+ * Enqueued right behind a pii_scan_redact_device* call it reads the spans and offsets that call wrote, with
+ * n_spans and batch_bytes known to the caller some other way.  It reads them as the call's FIRST run left them:
+ * a call that pii_sync has to run again (a work queue that overflowed, the long-row gate) wrote nothing usable,
+ * and the status word then says PII_REID_BAD_*.  pii_reserve and a first synced call of the workload's shape
+ * avoid the re-runs. */
+int pii_reidentify_device(struct pii_engine* e, const uint8_t* d_bytes, const uint64_t* d_offsets, uint32_t n_utt,
+                          uint64_t batch_base, uint64_t batch_bytes, const pii_span* d_spans, uint32_t n_spans,
+                          uint8_t* d_out_bytes, uint64_t out_cap, uint32_t* d_status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
