@@ -276,8 +276,8 @@ __device__ inline bool validate_src(int id, const S src, int n) {
 
 // luhn / nanp / ssn / ein / ipv4 in ONE pass: a wavefront whose lanes hold different validators
 // steps the match bytes once instead of once per validator kind (each kind's loop would run with the
-// lanes of the other kinds idle).  Same results as v_luhn ... v_ipv4 (which the IBAN / SWIFT / long
-// paths and the window kernels keep using).
+// lanes of the other kinds idle).  Same results as v_luhn ... v_ipv4, which only matches of more than
+// 32 bytes still reach (validate() below; the batch and the window kernels both call it).
 template <class S>
 __device__ inline bool v_digits(int id, const S src, int n) {
     int cnt = 0, sa = 0, sb = 0;                  // luhn

@@ -5506,7 +5506,8 @@ int grow_pairs(pii_engine* e, uint64_t cap) {
     return PII_OK;
 }
 
-int ensure_scratch(pii_engine* e, uint32_t n_utt, uint64_t bytes, uint32_t n_lanes, int min_len = 0) {
+int ensure_scratch(pii_engine* e, uint32_t n_utt, uint64_t bytes, uint32_t n_lanes, int min_len = 0,
+                   uint32_t cut_lanes = 2) {
     int rc = PII_OK;
     // event arenas: a lane's emitted positions + its utterance starts (ev_base); findings arenas:
     // one finding per min_len bytes + one per lane (fd_base; min_len 1 when external spans come in)
@@ -5548,11 +5549,15 @@ int ensure_scratch(pii_engine* e, uint32_t n_utt, uint64_t bytes, uint32_t n_lan
         e->cap_lanes = nl;
         e->cap_bsum = 0;
     }
-    // rows cut into lanes (k_chunk_index's long-row list): a long row is longer than long_min = 2 lanes,
-    // and lanes shrink to 2^MIN_LANE_SHIFT bytes for small batches -- so at most bytes / 256 of them
+    // rows cut into lanes (k_chunk_index's long-row list): a long row is longer than long_min = cut_lanes
+    // lanes (2, but PII_WIN_LONG's on the incremental re-scan), and lanes shrink to 2^MIN_LANE_SHIFT bytes
+    // for small batches -- so at most bytes / 256 of them at 2
     // (sizing this for 1 KiB lanes overflowed the list on a full window re-scan of 50k conversations,
-    // whose ~600-byte joined windows are all long rows of 256-byte lanes)
-    const uint64_t need_long = std::min<uint64_t>((uint64_t)n_utt + 1, bytes / (2u << MIN_LANE_SHIFT) + 2);
+    // whose ~600-byte joined windows are all long rows of 256-byte lanes; sizing it for 2 lanes under
+    // PII_WIN_LONG=1 overflowed it on a batch most of whose rows were of 129 .. 256 bytes).  cut_lanes 0:
+    // no row is cut, the size stays what it was
+    const uint64_t need_long = std::min<uint64_t>(
+        (uint64_t)n_utt + 1, bytes / ((uint64_t)(cut_lanes ? cut_lanes : 2u) << MIN_LANE_SHIFT) + 2);
     if (need_long > e->cap_long) {
         if ((rc = grow(e, e->long_rows, need_long))) return rc;
         e->cap_long = need_long;
@@ -5747,7 +5752,7 @@ int begin_call(pii_engine* e, const Call& c, const CallPlan& p, CallGeo& cg) {
     cg.n_chunks = lane_count(e, c.total);
     e->last_lanes = cg.n_chunks;
     e->excl_ran = false;
-    int rc = ensure_scratch(e, c.n_utt, c.total, cg.n_chunks, p.min_len);
+    int rc = ensure_scratch(e, c.n_utt, c.total, cg.n_chunks, p.min_len, p.cut_lanes);
     if (rc || ((p.ensure & ENS_QUEUES) && (rc = ensure_queues(e, c.total))) ||
         ((p.ensure & ENS_REDACT) && (rc = ensure_redact(e, c.span_cap, c.out_cap))) ||
         ((p.ensure & ENS_WINDOW) && (rc = ensure_window_scratch(e, c.n_utt))) ||
