@@ -420,11 +420,16 @@ def build_set_dfa(nfa: NFA, starts: Sequence[int], unanchored: bool, max_states:
     return minimize(dfa)
 
 
-def relax_items(items, budget: int):
+def relax_items(items, budget: int, skip_groups: bool = False):
     """Prefix relaxation for the SCAN prefilter: a pattern whose language, for every match of the
     original starting at s, has a match starting at s too (so SCAN reports a SUPERSET of starts;
     the exact FIRST DFA confirms each).  Bounded repeats are widened ({lo,hi} -> {min(lo,k)} X*),
-    the sequence is cut after `budget` consuming characters, an alternation ends the prefix."""
+    the sequence is cut after `budget` consuming characters, an alternation ends the prefix.
+    An optional or starred group of several items ends the prefix where it stands; with `skip_groups`
+    (add_relaxed: when that leaves nothing that consumes a character) it becomes the alternation of
+    its relaxed body and the relaxed rest of the sequence, and the prefix ends after that.  The rest is
+    what follows inside the enclosing group; a group that sets or clears a flag is not opened, so a pattern
+    whose optional group ends such a group before any required character, (?i:(?:ab)?)c, is still refused."""
     out = []
     for i, (op, av) in enumerate(items):
         if op == C.AT:
@@ -437,7 +442,12 @@ def relax_items(items, budget: int):
             budget -= 1
             continue
         if op == C.SUBPATTERN:
-            sub, full, budget = relax_items(list(av[-1]), budget)
+            if skip_groups and not av[1] and not av[2]:
+                # a group that changes no flag is its items in place, so that an optional group that ends it
+                # still has a rest: ((?:ab)?)c\d
+                r = relax_items(list(av[-1]) + list(items[i + 1:]), budget, True)
+                return out + r[0], r[1], r[2]
+            sub, full, budget = relax_items(list(av[-1]), budget, skip_groups)
             out.append((op, (av[0], av[1], av[2], sub)))
             if not full:
                 return out, False, 0
@@ -446,7 +456,7 @@ def relax_items(items, budget: int):
             # each alternative relaxed with the budget left; when every one of them is taken whole, the
             # prefix goes on past the alternation (with the smallest budget any alternative left), so a
             # pattern like (0?[1-9]|1[0-2])/... keeps its '/' instead of firing at every number
-            rs = [relax_items(list(b), budget) for b in av[1]]
+            rs = [relax_items(list(b), budget, skip_groups) for b in av[1]]
             out.append((op, (None, [r[0] for r in rs])))
             if not all(r[1] for r in rs):
                 return out, False, 0
@@ -458,9 +468,13 @@ def relax_items(items, budget: int):
             single = len(sub) == 1 and sub[0][0] in (C.LITERAL, C.NOT_LITERAL, C.ANY, C.IN)
             if not single:
                 if lo == 0:
+                    if skip_groups:
+                        # one repetition or more begins with the body, none with what follows the group
+                        out.append((C.BRANCH, (None, [relax_items(sub, budget, True)[0],
+                                                      relax_items(list(items[i + 1:]), budget, True)[0]])))
                     return out, False, 0
                 for _ in range(lo):
-                    s2, full, budget = relax_items(sub, budget)
+                    s2, full, budget = relax_items(sub, budget, skip_groups)
                     out.extend(s2)
                     if not full:
                         return out, False, 0
@@ -493,6 +507,9 @@ def add_relaxed(nfa: NFA, pattern: str, pid: int, budget: int, reverse: bool) ->
     items = list(tree)
     if budget > 0:
         items = relax_items(items, budget)[0]
+        if _items_nullable(items):
+            # the prefix ended at an optional group before any required character: (?:\+1[ -])?\d{3}-\d{4}
+            items = relax_items(list(tree), budget, skip_groups=True)[0]
     if _items_nullable(items):
         raise RuleError(f"relaxed pattern of {pattern!r} can match the empty string")
     m = nfa.add(MATCH, pid)

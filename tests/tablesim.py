@@ -42,6 +42,7 @@ class TableSim:
         self.k_off, self.k_ids = S["scan.k.acc_off"], S["scan.k.acc_ids"]
         self.det_type, self.det_val, self.det_lik = S["det.type"], S["det.validator"], S["det.lik"]
         self.first_desc = S["det.first_desc"].reshape(-1, 8)
+        self.first_pre = S["det.first_pre"]
         self.hot_rule = S["hot.rule"].reshape(-1, 4)
         self.hot_desc = S["hot.dfa_desc"].reshape(-1, 8)
         self.ptrans, self.pflags, self.pcmap = S["pool.trans"], S["pool.flags"], S["pool.cmap"]
@@ -119,9 +120,15 @@ class TableSim:
         return -1 if best == 1 << 30 else best
 
     # ---------------------------------------------------------------- FIRST / HOT runs
-    def first_run(self, p: int, text: bytes, s: int) -> int:
+    def first_run(self, p: int, text: bytes, s: int, pre: bool = False) -> int:
+        """pre: start the way first_begin does -- through the pattern's PRE row (compiler.add_first_drop), which
+        maps the byte before s to the start state, or to a terminal state for a start finditer always skips"""
         tr, fl, cm, nc, s0, s1, s2, _ = [int(x) for x in self.first_desc[p]]
         st = (s0, s1, s2)[K_BOT if s == 0 else _kind(text[s - 1])]
+        if pre and s > 0 and int(self.first_pre[p]) >= 0:
+            st = int(self.ptrans[tr + int(self.first_pre[p]) * nc + int(self.pcmap[cm + text[s - 1]])])
+            if int(self.pflags[fl + st]) & 2:
+                return -1
         last = -1
         for j in range(s, len(text)):
             st = int(self.ptrans[tr + st * nc + int(self.pcmap[cm + text[j]])])
@@ -162,7 +169,7 @@ class TableSim:
                 t = int(self.det_type[p])
                 if not self.enabled[v, t] or pos < cur[p]:
                     continue
-                e = self.first_run(p, text, pos)
+                e = self.first_run(p, text, pos, pre=True)
                 if e < 0:
                     continue
                 cur[p] = e
@@ -239,7 +246,7 @@ class TableSim:
                 p = int(self.d_ids[i])
                 if pos < cur[p]:
                     continue
-                e = self.first_run(p, text, pos)
+                e = self.first_run(p, text, pos, pre=True)
                 if e < 0:
                     continue
                 cur[p] = e

@@ -65,6 +65,39 @@ def test_first_dfa_matches_re(C, pat):
             assert _run_first(d, t, s) == want, (pat, t, s)
 
 
+def test_dialect_head_compiles_as_a_custom_type(C):
+    """DIALECT[0] through compile_rules (it was refused: its SCAN prefix reaches the optional group (?:ab) before
+    any required character): SCAN reports every true start, FIRST returns re's end, whole rows agree with the
+    oracle"""
+    import copy
+    from oracle import pii_oracle as O
+    from tablesim import TableSim
+    raw = copy.deepcopy(C.Rules.load().raw)
+    raw["inspect_config"]["custom_info_types"] = [
+        {"info_type": {"name": "HEAD"}, "regex": {"pattern": DIALECT[0]}, "likelihood": "LIKELY"}]
+    builtin = {"detectors": {"CVV_NUMBER": [{"pattern": r"\b\d{3,4}\b", "likelihood": "UNLIKELY"}]}}
+    comp = C.compile_rules(C.Rules(raw, builtin))
+    sim, ocfg = TableSim(comp), O.RuleConfig(raw, builtin)
+    pid = next(p.pid for p in comp.rules.patterns if p.type_name == "HEAD")
+    rx = re.compile(DIALECT[0].encode())
+    r = random.Random(17)
+    found = 0
+    for _ in range(800):
+        t = bytes(r.choice(b"ab 1") for _ in range(r.randrange(0, 14)))
+        ev = sim.scan(t, True)
+        reported = {pos for pos, sd, _ in ev
+                    if pid in sim.d_ids[int(sim.d_off[sim.d_accept(t, pos, sd)]):int(sim.d_off[sim.d_accept(t, pos, sd) + 1])]}
+        for s in range(len(t)):
+            m = rx.match(t, s)
+            assert sim.first_run(pid, t, s) == (m.end() if m else -1), (t, s)
+            if m:
+                assert s in reported, (t, s)
+        exp = [(f.start, f.end, f.type_id, f.likelihood) for f in O.find_pii(t, ocfg)]
+        assert sim.resolve(t, ev, 0) == exp, t
+        found += len(exp)
+    assert found > 800
+
+
 def test_rejects_unsupported(C):
     for bad in [r"a*", r"(a)\1", r"a(?=b)", r"x$", r"(?m)^x", r"(?:a*)*b"]:
         with pytest.raises(C.RuleError):
