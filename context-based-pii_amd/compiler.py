@@ -1294,10 +1294,14 @@ class Rules:
         # context keyword groups (main.py:558-578): group g -> (type, regex or None, always-hit)
         self.kw_groups = []
         for t, kws in self.context_keywords.items():
-            kws = [str(k) for k in (kws or [])]
-            always = any(k == "" for k in kws)
-            usable = [k for k in kws if k and k == k.lower()]   # upper-case keywords never hit lower()ed text
-            pat = "(?i)(?:" + "|".join(re.escape(k) for k in usable) + ")" if usable else None
+            # the keywords as extract_expected_pii compares them: UTF-8 bytes against the ASCII-lowered text
+            # (SURVEY A.8), so the pattern is a bytes pattern -- (?i) folds A-Z alone, and "café" is four
+            # literal bytes after "caf" that "CAFÉ" does not hold
+            kws = [str(k).encode("utf-8") for k in (kws or [])]
+            always = any(k == b"" for k in kws)
+            # a keyword with a byte of A-Z never hits the lowered text
+            usable = [k for k in kws if k and not any(65 <= c <= 90 for c in k)]
+            pat = b"(?i)(?:" + b"|".join(re.escape(k) for k in usable) + b")" if usable else None
             self.kw_groups.append((t, pat, always))
         # Every other info type becomes a keyword-less context group, so that a context record naming
         # it (call_dlp_for_redaction(transcript, {"expected_pii_type": t}), main.py:614-686) has a
@@ -1930,8 +1934,9 @@ _CACHE: Dict[str, Compiled] = {}
 def compile_default(dlp_config_path: Optional[str] = None, builtin_path: Optional[str] = None,
                     cache_dir: Optional[str] = None) -> Compiled:
     rules = Rules.load(dlp_config_path, builtin_path, fpe=True)
-    key = hashlib.sha256(json.dumps([rules.raw, [p.__dict__ for p in rules.patterns]], sort_keys=True,
-                                    default=str).encode()).hexdigest()[:16]
+    # (sort_keys hides the order of the context_keywords groups, which is their priority: it is listed)
+    key = hashlib.sha256(json.dumps([rules.raw, [p.__dict__ for p in rules.patterns], list(rules.context_keywords)],
+                                    sort_keys=True, default=str).encode()).hexdigest()[:16]
     if key in _CACHE:
         return _CACHE[key]
     c = compile_rules(rules, text_exclusions=True)
